@@ -26,6 +26,10 @@ median of those (inside the timed window the two marker packets 
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`, so both
 `python bench.py --gpus 8` and the driver's explicit torchrun command work.
 `--fwd-only` (BASELINE configs[1] with `--mode fp32 --rows 4096`): forward under no_grad, metric "(fwd)".
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the LAST timed step returned to its caller as DIR/<name>.npy --
+`loss` (float64, the criterion's output) and, unless --fwd-only, `grad_video` / `grad_text` (float32, the gradients w.r.t. the two
+inputs).  At most 64 MB in all: beyond that the gradients are a fixed, seeded sample of rows, named in `grad_rows` (float64 indices).
+The inputs depend on the arguments only (seed 1234 + rank), so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -89,6 +93,35 @@ def make_inputs(b, d, seed):
     v = torch.randn(b, d, generator=g)
     t = torch.randn(b, d, generator=g)
     return v, t
+
+
+DUMP_BYTES_MAX = 64 * 2**20
+
+
+def step_outputs(loss, v, t):
+    """Host copies of what one step hands its caller: the loss and (after backward) the two input gradients."""
+    out = {"loss": loss.detach().to("cpu", torch.float64, copy=True)}
+    if v.grad is not None:
+        out["grad_video"] = v.grad.detach().to("cpu", torch.float32, copy=True)
+        out["grad_text"] = t.grad.detach().to("cpu", torch.float32, copy=True)
+    return out
+
+
+def dump_outputs(outputs, path):
+    """DIR/<name>.npy for every output; gradients larger than the budget are cut to a fixed, seeded sample of rows (same rows for
+    both, listed in grad_rows.npy) so that the files stay within DUMP_BYTES_MAX."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    grads = [k for k in ("grad_video", "grad_text") if k in outputs]
+    total = sum(x.numel() * x.element_size() for x in outputs.values())
+    if grads and total > DUMP_BYTES_MAX:
+        rows, d = outputs[grads[0]].shape
+        rest = total - sum(outputs[k].numel() * outputs[k].element_size() for k in grads)
+        keep = (DUMP_BYTES_MAX - rest - 4096) // (len(grads) * d * 4 + 8)      # (4096: the .npy headers)
+        idx = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        outputs = dict(outputs, **{k: outputs[k][idx] for k in grads}, grad_rows=idx.to(torch.float64))
+    for name, x in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), x.numpy())
 
 
 def cpu_baseline(b, d, fwd_only=False):
@@ -390,7 +423,12 @@ def main():
     ap.add_argument("--influential", action="store_true",
                     help="BASELINE config 5: influential-sample pruning + loss weighting from synthetic input-space "
                          "features (crossclr_amd.CrossCLR); not the default workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's loss and input gradients (rank 0) as DIR/<name>.npy, "
+                         "at most 64 MB in all (a fixed, seeded sample of rows beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # RCCL prints a version banner on the C-level stdout of every rank.  Keep this process's stdout to
     # exactly ONE JSON line: everything else that lands on fd 1 is sent to stderr; the result goes to
@@ -488,6 +526,8 @@ def main():
             tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = tmax.item()
+        # (what the last timed step returned, copied out before anything else runs a step)
+        outputs = step_outputs(loss, v, t) if args.dump_outputs and rank == 0 else None
         # HIP events around every step of a SECOND pass of K steps, outside the timed region: an event record is a marker packet in the
         # stream, two per step cost the device 5 us per step (profiles/r05p_window.txt) -- the contract's window holds the steps alone
         ev = None if emu else [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
@@ -529,7 +569,7 @@ def main():
             gathered = [None] * world
             dist.all_gather_object(gathered, mine)
             per_rank = gathered
-        return {"t_step": elapsed / args.steps, "loss": float(loss.item()), "ev_ms": ev_ms, "per_rank": per_rank}
+        return {"t_step": elapsed / args.steps, "loss": float(loss.item()), "ev_ms": ev_ms, "per_rank": per_rank, "outputs": outputs}
 
     for _ in range(max(0, args.prewarm)):
         step()
@@ -613,6 +653,8 @@ def main():
         run = timed_run()
     t_step, loss_val, ev_ms, per_rank = run["t_step"], run["loss"], run["ev_ms"], run["per_rank"]
     B = b * world
+    if run["outputs"] is not None:
+        dump_outputs(run["outputs"], args.dump_outputs)
 
     if rank != 0:
         if world > 1:

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Generate the golden vectors under tests/golden/ by IMPORTING THE REFERENCE.
 
-Runs only in the build container (needs /root/reference).  The reference file
-itself never leaves that container: what is committed is data -- generator kind
-and seed, shapes, hyper-parameters, the SHA-256 of the inputs, and the
-reference's outputs (loss, gradients or gradient samples).
+Writing fixtures needs the reference's trainer/loss.py, named by the environment
+variable CROSSCLR_REFERENCE_FILE.  The reference file itself is never committed:
+what is committed is data -- generator kind and seed, shapes, hyper-parameters,
+the SHA-256 of the inputs, and the reference's outputs (loss, gradients or
+gradient samples).
 
 The reference hard-codes `.cuda()` for its masks (trainer/loss.py:66,103,104);
 in THIS process only, `torch.Tensor.cuda` is made the identity so the forward
@@ -17,6 +18,10 @@ every case it can afford to run twice, and refuses to write fixtures otherwise.
     python tests/golden/make_golden.py --check    # regenerate in memory, compare with the committed
                                                   # index.json / *.npz bit for bit, write nothing
     python tests/golden/make_golden.py --check --only g1_b64_d256_s0 g2_b8_d16_s1
+
+`--check` without CROSSCLR_REFERENCE_FILE regenerates every case through the oracle's op-for-op
+form in the reference's place (the form this script proved bit-identical to the reference when
+it wrote the fixtures): the recipe -> fixture path is then checked on any machine.
 
 The reference module is loaded BY FILE PATH under the private name `ref_loss` (the repository
 has its own `trainer/loss.py` drop-in shim, so `import trainer.loss` would find the product, not
@@ -35,13 +40,15 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-REFERENCE_FILE = os.environ.get("CROSSCLR_REFERENCE_FILE", "/root/reference/trainer/loss.py")
+REFERENCE_FILE = os.environ.get("CROSSCLR_REFERENCE_FILE")
 
 
 def load_reference():
-    """The reference class, loaded from its file (never through `import trainer.loss`)."""
+    """The reference class, loaded from its file (never through `import trainer.loss`); None without one."""
+    if not REFERENCE_FILE:
+        return None
     if not os.path.exists(REFERENCE_FILE):
-        raise SystemExit(f"{REFERENCE_FILE} not found: this script runs only in the build container")
+        raise SystemExit(f"CROSSCLR_REFERENCE_FILE={REFERENCE_FILE} not found")
     spec = importlib.util.spec_from_file_location("ref_loss", REFERENCE_FILE)
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
@@ -68,6 +75,8 @@ def sha(*tensors):
 
 
 def run_reference(v, t, tau, w):
+    if Reference is None:       # (--check only: the oracle's op-for-op form stands in for the reference)
+        return orc.eager_loss_and_grads(v, t, tau, w)
     v = v.detach().clone().requires_grad_(True)
     t = t.detach().clone().requires_grad_(True)
     crit = Reference(temperature=tau, negative_weight=w)
@@ -144,6 +153,8 @@ def main():
     ap.add_argument("--only", nargs="*", default=None, help="restrict to these case names")
     args = ap.parse_args()
     CHECK["on"], CHECK["only"] = args.check, (set(args.only) if args.only else None)
+    if Reference is None and not args.check:
+        raise SystemExit("writing fixtures needs the reference: set CROSSCLR_REFERENCE_FILE to its trainer/loss.py")
     torch.manual_seed(0)
 
     class _Metas(list):
@@ -203,7 +214,8 @@ def main():
     if args.check:
         if CHECK["bad"] or not CHECK["seen"]:
             raise SystemExit(f"golden check FAILED: {CHECK['bad'] or 'no case selected'}")
-        print(f"golden check ok: {CHECK['seen']} cases regenerated from {REFERENCE_FILE} match the committed fixtures")
+        source = REFERENCE_FILE or "the oracle's op-for-op form (no CROSSCLR_REFERENCE_FILE)"
+        print(f"golden check ok: {CHECK['seen']} cases regenerated from {source} match the committed fixtures")
         return
     out = os.path.join(HERE, "index.json")
     prev = {}

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import torch
 
 from oracle import crossclr_oracle as orc
@@ -47,6 +48,39 @@ def test_bench_single_rank_line_on_the_emulated_kernels():
     assert out["value"] > 0 and out["higher_is_better"] is True and out["scaling"] == "weak" and out["vs_baseline"] is None
     v, t = orc.make_inputs("randn", 32, 32, 1234)
     assert abs(out["loss"] - float(orc.streaming_stats(v, t, 0.03, 0.8)["loss"])) < 1e-4
+
+
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: the loss and both input gradients of the last timed step as .npy files, the same from run to run."""
+    args = ["--selftest-emu", "--rows", "32", "--dim", "32", "--steps", "2", "--warmup", "1", "--prewarm", "0", "--mode", "fp32"]
+    out = _run(args + ["--dump-outputs", str(tmp_path / "a")])
+    _run(args + ["--dump-outputs", str(tmp_path / "b")])
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("loss", "grad_video", "grad_text")}
+    assert sorted(os.listdir(tmp_path / "a")) == ["grad_text.npy", "grad_video.npy", "loss.npy"]
+    assert got["loss"].dtype == np.float64 and got["loss"].shape == () and float(got["loss"]) == out["loss"]
+    assert got["grad_video"].dtype == np.float32 and got["grad_video"].shape == (32, 32) == got["grad_text"].shape
+    for n, x in got.items():
+        assert np.array_equal(x, np.load(tmp_path / "b" / (n + ".npy"))), n
+    v, t = orc.make_inputs("randn", 32, 32, 1234)
+    _, gv, gt = orc.eager_loss_and_grads(v, t, 0.03, 0.8)
+    scale = max(gv.abs().max().item(), gt.abs().max().item())
+    assert np.abs(got["grad_video"] - gv.numpy()).max() <= 1e-4 * scale
+    assert np.abs(got["grad_text"] - gt.numpy()).max() <= 1e-4 * scale
+
+
+def test_bench_dump_outputs_samples_rows_beyond_the_size_cap(tmp_path, monkeypatch):
+    b = _bench_module()
+    monkeypatch.setattr(b, "DUMP_BYTES_MAX", 64 * 1024)
+    g = torch.arange(1000 * 16, dtype=torch.float32).reshape(1000, 16)
+    outputs = {"loss": torch.tensor(1.5, dtype=torch.float64), "grad_video": g, "grad_text": -g}
+    b.dump_outputs(outputs, str(tmp_path / "x"))
+    b.dump_outputs(outputs, str(tmp_path / "y"))
+    rows = np.load(tmp_path / "x" / "grad_rows.npy")
+    gv, gt = np.load(tmp_path / "x" / "grad_video.npy"), np.load(tmp_path / "x" / "grad_text.npy")
+    assert rows.dtype == np.float64 and 400 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    assert sum(os.path.getsize(tmp_path / "x" / f) for f in os.listdir(tmp_path / "x")) <= b.DUMP_BYTES_MAX
+    assert np.array_equal(gv, g.numpy()[rows.astype(np.int64)]) and np.array_equal(gt, -gv)
+    assert np.array_equal(rows, np.load(tmp_path / "y" / "grad_rows.npy"))
 
 
 def test_bench_gpus2_spawns_itself_and_reports_the_global_loss():
