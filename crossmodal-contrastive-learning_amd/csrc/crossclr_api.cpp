@@ -75,14 +75,13 @@ static const float* const kNoF = nullptr;     // (kernel arguments a launch does
 
 // tuning knobs from the environment, read ONCE per process (not per call: crossclr_make_plan sits on the step's host path)
 struct EnvKnobs {
-    bool disable_fast, disable_symmetric, disable_save, bwd_dc256, disable_xf;
+    bool disable_fast, disable_symmetric, disable_save, disable_xf;
     int bwd_kernel, fwd_blocks, bwd_slices;
     EnvKnobs() {
         disable_fast = getenv("CROSSCLR_DISABLE_FAST") != nullptr;
         disable_symmetric = getenv("CROSSCLR_DISABLE_SYMMETRIC") != nullptr;
         disable_save = getenv("CROSSCLR_DISABLE_SAVE") != nullptr;
         disable_xf = getenv("CROSSCLR_DISABLE_XF") != nullptr;  // no fragment-major operand copy: the saved backward stages the column tiles through LDS
-        bwd_dc256 = getenv("CROSSCLR_BWD_DC256") != nullptr;    // generic backward: D slices of 256 columns even where 512 divides Dpad (A/B)
         const char* e = getenv("CROSSCLR_BWD_KERNEL");
         bwd_kernel = e ? atoi(e) : 0;
         e = getenv("CROSSCLR_FWD_BLOCKS");
@@ -244,10 +243,7 @@ extern "C" int crossclr_make_plan(int b, int D, int world, int rank, int mode, c
         plan->bwd_slices = sl;
     }
     {
-#ifndef CROSSCLR_FINISH_LPR
-#define CROSSCLR_FINISH_LPR 4
-#endif
-        const int rows_per_block = 256 / CROSSCLR_FINISH_LPR;
+        const int rows_per_block = 256 / kFinishLpr;
         int nb = (2 * plan->bpad + rows_per_block - 1) / rows_per_block;      // finish kernels: 256 / LPR rows per block, grid-stride beyond
         if (nb > 1024) nb = 1024;
         plan->loss_ws_doubles = 1 + nb;
@@ -404,8 +400,7 @@ static int project_pack_t(const crossclr_plan* p, const void* xv, const void* xt
     Geo g; memset(&g, 0, sizeof(g));
     g.b = p->b; g.bpad = p->bpad; g.D = p->D; g.Dpad = p->Dpad;
     // 64 rows per block up to Dpad = 512 when that still gives every CU a block; 32 rows otherwise (and always above 512: accumulators)
-    static const int rows_knob = [] { const char* e = getenv("CROSSCLR_PROJECT_ROWS"); return e ? atoi(e) : 0; }();      // 32 / 64: tuning knob (A/B)
-    const bool rows32 = rows_knob == 32 || (rows_knob != 64 && p->bpad / 64 < 256);
+    const bool rows32 = p->bpad / 64 < 256;
     dim3 grid(p->bpad / 64), grid32(p->bpad / 32), block(256);
 #define CROSSCLR_LPPX(DKP, RFV, GRID) LAUNCH((project_pack_kernel<TIN, DKP, RFV, WF>), GRID, block, stream, (const TIN*)xv, (const TIN*)xt, ldv, ldt, Din_v, Din_t, \
                                              (const bf16_t*)wv, (const bf16_t*)wt, ldw_v, ldw_t, bv, bt, g, (bf16_t*)xhat, inv_norm, diag)
@@ -1051,7 +1046,7 @@ static int backward_generic(const crossclr_plan* p, const Geo& g, const void* ro
         if (shift_rows) { if (krows) CROSSCLR_LB2(DC, true, true); else CROSSCLR_LB2(DC, false, true); }   \
         else { if (krows) CROSSCLR_LB2(DC, true, false); else CROSSCLR_LB2(DC, false, false); }            \
     } while (0)
-    if (p->Dpad % 512 == 0 && !env_knobs().bwd_dc256) CROSSCLR_LB(512);
+    if (p->Dpad % 512 == 0) CROSSCLR_LB(512);
     else if (p->Dpad % 256 == 0) CROSSCLR_LB(256);
     else if (p->Dpad % 128 == 0) CROSSCLR_LB(128);
     else CROSSCLR_LB(64);

@@ -31,18 +31,7 @@
 
 namespace crossclr {
 
-#ifndef CROSSCLR_DSL_PE
-#define CROSSCLR_DSL_PE 3      // tiles between the DMA of a saved-exponential tile and its use (HBM latency)
-#endif
-#ifndef CROSSCLR_DSL_STAGGER
-#define CROSSCLR_DSL_STAGGER 0  // 1: four copies of the loop, one per wave, whose VMEM instructions sit in different MFMA slots (measured: the
-                               // addresser's FIFO-full events drop 5x, the time does not move; 4x the code and compile time) -- off
-#endif
-#ifndef CROSSCLR_DABL
-#define CROSSCLR_DABL 0        // timing ablations (WRONG results): bit0 no E DMA, bit1 no X DMA, bit2 no weight VALU, bit3 no W write,
-                               // bit4 no B reads, bit5 no barrier, bit6 no A reads, bit7 no MFMA, bit8 E from a 2-MiB window, bit9 X from 8 tiles,
-                               // bit10 no mid-iteration LDS wait, bit11 no closing LDS wait, bit12 no closing VMEM wait
-#endif
+constexpr int kDslPE = 3;      // tiles between the DMA of a saved-exponential tile and its use (HBM latency)
 
 #ifndef CROSSCLR_EMU
 template <int OFF> __device__ __forceinline__ unsigned lds_read_b32_async(unsigned addr) {
@@ -61,7 +50,6 @@ template <typename T> __device__ __forceinline__ void pin_s(T& x) {
 }
 template <typename T> __device__ __forceinline__ void pin_v(T& x) { asm volatile("" : "+v"(x)); }
 __device__ __forceinline__ void mfma_acc(f32x16& acc, bf16x8 a, bf16x8 b) {
-    if (CROSSCLR_DABL & 128) { asm volatile("" : "+a"(acc) : "v"(a), "v"(b)); return; }
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
 }
 // XF: an MFMA B fragment straight from global memory into VGPRs (buffer_load_dwordx4 ... offen: wave-uniform descriptor in SGPRs,
@@ -103,9 +91,9 @@ __device__ __forceinline__ void wait_lgkm_all() {}
 __device__ __forceinline__ void mfma_acc(f32x16& acc, bf16x8 a, bf16x8 b) { acc = mfma_32x32x16_bf16(a, b, acc); }
 #endif
 
-// One wave's share of the block (WV = its index, a compile-time constant: the four waves run four copies of the loop whose
-// VMEM instructions sit in DIFFERENT MFMA slots -- see the schedule below -- and whose LDS addresses are immediates).
-template <int DK, bool SW, int MODE, int XP, int TPRF, int WV, bool XF = false>
+// One wave's share of the block (one copy of the loop for all four waves: copies per wave whose VMEM instructions sit in different
+// MFMA slots were measured -- the addresser's FIFO-full events drop 5x, the time does not move; 4x the code and compile time).
+template <int DK, bool SW, int MODE, int XP, int TPRF, bool XF = false>
 __device__ __forceinline__ void dsl_wave(unsigned char* lds, const bf16_t* cols, const unsigned char* stash, const Geo& g, const float* rz, const float* wrz,
         const float* rz_cols, const float* wrz_cols, float* gbuf, int accumulate, int tiles_per_slice, const float* ks, const float* kc) {
     constexpr int RB = DK * 32;            // bytes per row of the (part of the) operand a block multiplies
@@ -116,7 +104,7 @@ __device__ __forceinline__ void dsl_wave(unsigned char* lds, const bf16_t* cols,
     constexpr int DI = DK / 8;             // 32-wide output fragments per wave (its column slice)
     constexpr int H = 4 * DI;              // MFMAs per k-step: 4 row groups x DI fragments
     constexpr int NSX = XF ? 0 : 3;        // column-tile ring (XF: the column tile never touches LDS)
-    constexpr int PE = XF ? 2 : CROSSCLR_DSL_PE;
+    constexpr int PE = XF ? 2 : kDslPE;
     constexpr int NSE = PE + 1;            // saved-exponential + statistics rings (private to a wave)
     constexpr int ESTG = 4 * 2048;         // one stage of the E ring: [4 waves][2 KiB]
     constexpr int SSTG = 4 * 256;          // one stage of a statistics ring: [4 waves][64 floats] (the tile's 32 + 32 spare)
@@ -127,7 +115,7 @@ __device__ __forceinline__ void dsl_wave(unsigned char* lds, const bf16_t* cols,
     constexpr int O0 = K0 + (SW ? NSE * SSTG : 0);      // the block's own statistics: rz[128] | wrz[128] | k[128]
     static_assert(DK % 8 == 0 && DK >= 8 && DK <= 32, "Dpad (per part) in {128, 256, 384, 512}");
     static_assert(XF || PE >= 3, "E / statistics of tile t+2 must be older than the pieces of X(t+1)");
-    static_assert(!XF || (MODE == 0 && WV < 0 && NXO == 2 * DI), "XF: the local symmetric block, one copy of the loop");
+    static_assert(!XF || (MODE == 0 && NXO == 2 * DI), "XF: the local symmetric block");
     static_assert(O0 + 3 * 512 <= 160 * 1024, "LDS budget");
     // XF ("fragment-major" column operand, crossclr_normalize_xf): `cols` is not the row-major packed operand but XF[tile u = 32 stacked
     // rows][dt = Dpad/32 column fragments][k-step][lane][8 bf16] -- 1 KiB per (u, dt, k-step), inside it lane (n = lane & 31, kg = lane >> 5)
@@ -146,8 +134,7 @@ __device__ __forceinline__ void dsl_wave(unsigned char* lds, const bf16_t* cols,
     // segments per stash row, g.skip_rank = the partner's segment inside it.
     constexpr bool RECT = MODE == 1, TR = MODE == 2;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = WV >= 0 ? WV : uniform(tid >> 6);        // WV = -1: one copy of the code for all four waves
-    constexpr int WVS = WV >= 0 ? WV : 0;                     // the wave's place in the VMEM schedule
+    const int wave = uniform(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
     const int row0b = blockIdx.x * 128;
     const int row0w = row0b + 32 * wave;
@@ -253,15 +240,13 @@ __device__ __forceinline__ void dsl_wave(unsigned char* lds, const bf16_t* cols,
     // the local block's cursors are functions of the tile index alone (two scalar instructions); rectangular launches walk segments
     auto col_of = [&](int u) { u = clampt(u); return Col{u, u, 0, u}; };
     auto issue_x_piece = [&](const Col& c, int stage, int k) {
-        if (CROSSCLR_DABL & 2) return;
-        lds_dma16_buf(rs_x, voffx[k], (unsigned)((CROSSCLR_DABL & 512) ? (c.mt & 7) : c.mt) * (unsigned)(QT * RBG), lds + stage * TILE + (wave + 4 * k) * 1024);
+        lds_dma16_buf(rs_x, voffx[k], (unsigned)c.mt * (unsigned)(QT * RBG), lds + stage * TILE + (wave + 4 * k) * 1024);
     };
     // XF: fragment (di, ks) of column tile c into register set `setc`
     auto load_xf = [&](auto setc, auto dic, auto ksc, const Col& c) {
         constexpr int S = decltype(setc)::value, di = decltype(dic)::value, ks = decltype(ksc)::value;
-        if (CROSSCLR_DABL & 2) return;
         constexpr int off = (2 * di + ks) * 1024;
-        unsigned so = (unsigned)((CROSSCLR_DABL & 512) ? (c.mt & 7) : c.mt) * (unsigned)(QT * RBG);
+        unsigned so = (unsigned)c.mt * (unsigned)(QT * RBG);
         pin_s(so);
         BS[S][di][ks] = buf_load_b128_async<(off & 4095)>(rs_xf, off >= 4096 ? xfv1 : xfv0, so);
     };
@@ -308,9 +293,8 @@ __device__ __forceinline__ void dsl_wave(unsigned char* lds, const bf16_t* cols,
     };
     // piece 0 / 1: the wave's 2-KiB stash tile as stored (lane-linear); piece 2: the tile's statistics; piece 3 (SW): its k
     auto issue_e_piece = [&](const Col& c, const unsigned char* etile, int estage, int k) {
-        if (CROSSCLR_DABL & 1) return;
         if (k < 2) {
-            const BufRsrc rs_e = make_rsrc((CROSSCLR_DABL & 256) ? stash + ((size_t)(etile - stash) & (size_t)0x1FF800) : etile, 2048u);
+            const BufRsrc rs_e = make_rsrc(etile, 2048u);
             lds_dma16_buf(rs_e, (unsigned)(lane * 16 + 1024 * k), 0u, ebuf + estage * ESTG + 1024 * k);
         } else if (k == 2) {
             const bool same = col_mod(c) == rmod;
@@ -376,12 +360,11 @@ __device__ __forceinline__ void dsl_wave(unsigned char* lds, const bf16_t* cols,
             // (one expression for every tile of a weighted launch: scales of 1.0 for the other modality's tiles give rs + cs exactly;
             //  crossclr_kernels_dslp.h forms the same FMA from ones it reads out of LDS)
             const float zz = SW ? __builtin_fmaf(rs, kq[j], cs[j] * (weighted ? kr : 1.f)) : (rs + cs[j]);
-            pk[th].e[4 * r4 + j] = (CROSSCLR_DABL & 4) ? ev.e[4 * r4 + j] : f32_to_bf16_bits(v * zz);
+            pk[th].e[4 * r4 + j] = f32_to_bf16_bits(v * zz);
         }
     };
     auto write_w = [&](auto mir, int wslot, const Bits8 (&pk)[2]) {
         constexpr bool MIR = decltype(mir)::value;
-        if (CROSSCLR_DABL & 8) return;
         unsigned char* wb = lds + W0 + wslot * WBUF;
         if (MIR) {
             *reinterpret_cast<u32x4*>(wb + wr_mir) = __builtin_bit_cast(u32x4, pk[0]);
@@ -427,7 +410,7 @@ __device__ __forceinline__ void dsl_wave(unsigned char* lds, const bf16_t* cols,
             }
         }
         cw = col_at(t);
-        if (!(CROSSCLR_DABL & 3)) wait_dma_keep<(NSE - 1) * NEO + (XF ? 0 : (NSX - 1) * NXO)>();   // E / statistics of the first tile (XF: and X(t))
+        wait_dma_keep<(NSE - 1) * NEO + (XF ? 0 : (NSX - 1) * NXO)>();   // E / statistics of the first tile (XF: and X(t))
         if constexpr (XF) xf_landed(IdxC<0>{});
         {
             Bits8 pk[2];
@@ -449,8 +432,8 @@ __device__ __forceinline__ void dsl_wave(unsigned char* lds, const bf16_t* cols,
             }
         }
         col_next(cw);
-        if constexpr (XF) { if (!(CROSSCLR_DABL & 3)) wait_dma_keep<(NSE - 2) * NEO>(); }     // E(t+1): the first iteration stages it at once
-        else if (!(CROSSCLR_DABL & 3)) wait_dma_keep<(NSX - 2) * NXO>();     // X(t) (and every E piece: they were issued first)
+        if constexpr (XF) wait_dma_keep<(NSE - 2) * NEO>();     // E(t+1): the first iteration stages it at once
+        else wait_dma_keep<(NSX - 2) * NXO>();     // X(t) (and every E piece: they were issued first)
         barrier_keep_dma();
         timing_mark(1);
         int sx = 0, se = 1 % NSE, wslot = 0;
@@ -495,33 +478,25 @@ __device__ __forceinline__ void dsl_wave(unsigned char* lds, const bf16_t* cols,
                 constexpr int pi = decltype(pic)::value, th = decltype(thc)::value;
                 if (MC) {
                     Pair p;
-                    if (CROSSCLR_DABL & 64) p = __builtin_bit_cast(Pair, A1c[pi]);
-                    else {
-                        p.lo = lds_read_tr16_b64_async<pi * 2048 + th * 1024>(wa);
-                        p.hi = lds_read_tr16_b64_async<pi * 2048 + th * 1024 + 512>(wa);
-                    }
+                    p.lo = lds_read_tr16_b64_async<pi * 2048 + th * 1024>(wa);
+                    p.hi = lds_read_tr16_b64_async<pi * 2048 + th * 1024 + 512>(wa);
                     if (th) Am1[pi] = p; else Am0[pi] = p;
                 } else {
-                    const u32x4 v = (CROSSCLR_DABL & 64) ? __builtin_bit_cast(u32x4, A1c[pi]) : lds_read_b128_async<pi * 2048 + th * 1024>(wa);
+                    const u32x4 v = lds_read_b128_async<pi * 2048 + th * 1024>(wa);
                     if (th) Ad1[pi] = v; else Ad0[pi] = v;
                 }
             };
             auto read_b = [&](auto dic, auto thc) {
                 constexpr int di = decltype(dic)::value, th = decltype(thc)::value;
                 Pair p;
-                if (CROSSCLR_DABL & 16) p = __builtin_bit_cast(Pair, B1c[di]);
-                else {
-                    p.lo = lds_read_tr16_b64_async<(16 * th) * RB>(xa + bo[di][0]);
-                    p.hi = lds_read_tr16_b64_async<(16 * th + 8) * RB>(xa + bo[di][1]);
-                }
+                p.lo = lds_read_tr16_b64_async<(16 * th) * RB>(xa + bo[di][0]);
+                p.hi = lds_read_tr16_b64_async<(16 * th + 8) * RB>(xa + bo[di][1]);
                 if (th) B1[di] = p; else B0[di] = p;
             };
             // ---- VMEM: NV = NXO + NEO pieces per wave and iteration, dealt evenly over the 2 H slots: first the pieces of X(t+2), THEN the
             // saved exponentials / statistics of tile t+1+PE.  The order matters: vmcnt retires in order, so the wait that proves
             // X(t+1) landed also waits for everything issued before it -- with E first, every iteration waited for an HBM access it had
             // issued only one tile earlier (measured: 0.024 ms of the kernel; E from an L2-resident window took it away).
-            // (CROSSCLR_DSL_STAGGER: piece j of wave WV sits in slot floor((NV WV + j) 2H / (4 NV)) instead -- each wave in its own
-            // quarter of the iteration, one wave at a time talking to the texture addresser.)
             constexpr int NV = NEO + NXO;
             constexpr int R2 = H / 2 > 0 ? H / 2 : 1;                // second half: slots for the reads / for the half-quads
             constexpr int WSLOT = 1 + R2 <= H - 1 ? 1 + R2 : H - 1;  // ... slot of the W write
@@ -541,7 +516,7 @@ __device__ __forceinline__ void dsl_wave(unsigned char* lds, const bf16_t* cols,
                             constexpr int je = j - NXO;
                             if constexpr (H + 1 + (je * (ADV - H - 1)) / (NEO - 1) == s) issue_e_piece(ce, etile, se_free, je);
                         }
-                    } else if constexpr ((WV >= 0 ? ((NV * WVS + j) * ADV) / (4 * NV) : (j * ADV) / NV) == s) {
+                    } else if constexpr ((j * ADV) / NV == s) {
                         if constexpr (j < NXO) issue_x_piece(cx, sx_free, j);
                         else issue_e_piece(ce, etile, se_free, j - NXO);
                     }
@@ -590,7 +565,7 @@ __device__ __forceinline__ void dsl_wave(unsigned char* lds, const bf16_t* cols,
                     items1(sc);
                     vmem_items(sc);
                     if constexpr (s == H - 1) {
-                        if (!(CROSSCLR_DABL & 1024)) wait_lgkm_all();
+                        wait_lgkm_all();
                         staged_landed(IdxC<MN>{}, st);
 #pragma unroll
                         for (int p = 0; p < 4; ++p) { if (MC) { after_wait(Am0[p].lo); after_wait(Am0[p].hi); } else after_wait(Ad0[p]); }
@@ -619,7 +594,7 @@ __device__ __forceinline__ void dsl_wave(unsigned char* lds, const bf16_t* cols,
                 sched_fence();
             });
             // k-step 1 of this tile has been read (and W(t+1) written): all LDS traffic of the iteration is complete ...
-            if (!(CROSSCLR_DABL & 2048)) wait_lgkm_all();
+            wait_lgkm_all();
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 if (MC) { after_wait(Am1[p].lo); after_wait(Am1[p].hi); A1c[p] = __builtin_bit_cast(bf16x8, Am1[p]); }
@@ -642,13 +617,13 @@ __device__ __forceinline__ void dsl_wave(unsigned char* lds, const bf16_t* cols,
             // (operations issued after X(t+1)'s last piece: the E pieces of the previous iteration and everything of this one; the
             // first iteration's X(t+1) is the last operation of the prologue -- only this iteration's operations follow it)
             if constexpr (XF) {      // tile t+1's fragments have landed: only this iteration's NEO pieces were issued behind the last of them
-                if (!(CROSSCLR_DABL & (3 | 4096))) wait_dma_keep<NEO>();
+                wait_dma_keep<NEO>();
                 xf_landed(IdxC<PAR ^ 1>{});
-            } else if (!(CROSSCLR_DABL & (3 | 4096))) {
+            } else {
                 if (first_iter) wait_dma_keep<NXO + NEO>(); else wait_dma_keep<NXO + 2 * NEO>();
             }
             first_iter = false;
-            if (!(CROSSCLR_DABL & 32)) barrier_keep_dma();
+            barrier_keep_dma();
         };
         if constexpr (XF) {
             // The loop unrolled by two: iteration parity = register set of its tile.  Every phase (M->M, M->D, D->D) starts on set 0; a phase
@@ -737,7 +712,7 @@ __global__ void __launch_bounds__(256, 1) fast_bwd_dsl_kernel(const bf16_t* cols
     constexpr int DI = DK / 8;             // 32-wide output fragments per wave (its column slice)
     constexpr int H = 4 * DI;              // MFMAs per k-step: 4 row groups x DI fragments
     constexpr int NSX = XF ? 0 : 3;        // column-tile ring
-    constexpr int PE = XF ? 2 : CROSSCLR_DSL_PE;
+    constexpr int PE = XF ? 2 : kDslPE;
     constexpr int NSE = PE + 1;            // saved-exponential + statistics rings (private to a wave)
     constexpr int ESTG = 4 * 2048;         // one stage of the E ring: [4 waves][2 KiB]
     constexpr int SSTG = 4 * 256;          // one stage of a statistics ring: [4 waves][64 floats] (the tile's 32 + 32 spare)
@@ -761,17 +736,7 @@ __global__ void __launch_bounds__(256, 1) fast_bwd_dsl_kernel(const bf16_t* cols
         own[256 + tid] = SW ? ks[row0b + tid] : 1.f;
     }
     __syncthreads();        // (before any LDS-DMA is in flight: this barrier may drain VMEM)
-#if !CROSSCLR_DSL_STAGGER
-    if constexpr (XF) { dsl_wave<DK, SW, MODE, XP, TPRF, -1, true>(lds, cols, stash, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tiles_per_slice, ks, kc); return; }
-    dsl_wave<DK, SW, MODE, XP, TPRF, -1>(lds, cols, stash, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tiles_per_slice, ks, kc);
-#else
-    switch (uniform(tid >> 6)) {
-        case 0: dsl_wave<DK, SW, MODE, XP, TPRF, 0>(lds, cols, stash, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tiles_per_slice, ks, kc); break;
-        case 1: dsl_wave<DK, SW, MODE, XP, TPRF, 1>(lds, cols, stash, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tiles_per_slice, ks, kc); break;
-        case 2: dsl_wave<DK, SW, MODE, XP, TPRF, 2>(lds, cols, stash, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tiles_per_slice, ks, kc); break;
-        default: dsl_wave<DK, SW, MODE, XP, TPRF, 3>(lds, cols, stash, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tiles_per_slice, ks, kc); break;
-    }
-#endif
+    dsl_wave<DK, SW, MODE, XP, TPRF, XF>(lds, cols, stash, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tiles_per_slice, ks, kc);
 }
 
 }  // namespace crossclr

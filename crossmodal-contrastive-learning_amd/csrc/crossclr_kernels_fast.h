@@ -95,11 +95,9 @@ __device__ __forceinline__ void lds_dma4_buf(const BufRsrc& b, unsigned voff, un
 //  survives ~8 tiles; with sc1 the L2 belongs to the column tiles, which is what makes the XCD-aware range placement (fwd_make_perm) work:
 //  FETCH_SIZE 224 -> 71 MB per launch, forward_save -7 % (profiles/r04_ab_fwd_xcd*.txt; sc1 alone: the same counters, ~1 % slower).
 //  The nt hint on the backward's stash LOADS costs +3.7 %: every tile is read twice.)
-#ifndef CROSSCLR_STASH_AUX
-#define CROSSCLR_STASH_AUX 18      // cache policy of the stash stores: 2 = nt, 16 = sc1, 18 = sc1 | nt (A/B: tools/ab_fwd_xcd.sh)
-#endif
+constexpr int kStashStoreAux = 18;      // cache policy of the stash stores: sc1 | nt (profiles/r04_ab_fwd_xcd*.txt)
 __device__ __forceinline__ void buf_store16(const BufRsrc& b, unsigned voff, unsigned soff, u32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, b.r, (int)voff, (int)soff, CROSSCLR_STASH_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(v, b.r, (int)voff, (int)soff, kStashStoreAux);
 }
 __device__ __forceinline__ void buf_store4(const BufRsrc& b, unsigned voff, unsigned soff, float v) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), b.r, (int)voff, (int)soff, 0);
@@ -160,32 +158,12 @@ template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
     static_for_seq(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
 }
 
-// Tuning switches (compile-time; defaults = best measured on MI355X, see profiles/):
-//   CROSSCLR_PF     LDS fragment reads kept in flight ahead of the MFMA that consumes them
-//   CROSSCLR_SCHED  0 none, 1 iglp_opt(0), 2 iglp_opt(1), 3 explicit sched_group_barrier pipeline
-//                   {PF x reads ; (1 MFMA ; reads)*}: without it hipcc re-places the reads right in
-//                   front of their MFMA (lgkmcnt(0) before every MFMA)
-//   CROSSCLR_ABL    timing ablations of the fast backward (results are WRONG; tuning only):
-//                   bit0 skip second product, bit1 skip exp/weights, bit2 skip first product, bit3 skip DMA+barriers,
-//                   bit4 second product without its LDS reads, bit5 first product without its LDS reads
-#ifndef CROSSCLR_PF
-#define CROSSCLR_PF 4
-#endif
-#ifndef CROSSCLR_SCHED
-#define CROSSCLR_SCHED 3
-#endif
-#ifndef CROSSCLR_ABL
-#define CROSSCLR_ABL 0
-#endif
-#ifndef CROSSCLR_G1CHAINS
-#define CROSSCLR_G1CHAINS 1   // accumulator chains of the 32-row backward's first product (2: measured)
-#endif
-#if defined(CROSSCLR_EMU) || CROSSCLR_SCHED == 0
+// LDS fragment reads kept in flight ahead of the MFMA that consumes them (best measured on MI355X, see profiles/)
+constexpr int kFastPF = 4;
+// explicit sched_group_barrier pipeline {PF x reads ; (1 MFMA ; reads)*}: without it hipcc re-places the reads right in front of
+// their MFMA (lgkmcnt(0) before every MFMA); iglp_opt and no scheduling were measured slower (profiles/)
+#ifdef CROSSCLR_EMU
 #define SCHED_PIPELINE(nmfma, reads_per_mfma, pf) do {} while (0)
-#elif CROSSCLR_SCHED == 1
-#define SCHED_PIPELINE(nmfma, reads_per_mfma, pf) __builtin_amdgcn_iglp_opt(0)
-#elif CROSSCLR_SCHED == 2
-#define SCHED_PIPELINE(nmfma, reads_per_mfma, pf) __builtin_amdgcn_iglp_opt(1)
 #else
 #define SCHED_PIPELINE(nmfma, reads_per_mfma, pf)                                                      \
     do {                                                                                               \
@@ -197,17 +175,8 @@ template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
     } while (0)
 #endif
 
-#ifndef CROSSCLR_TUNE
-#define CROSSCLR_TUNE 0   // A/B switches: bit0 (unused), bit1 no per-MFMA fence in fast_bwd16_kernel, bit2 draining barrier there
-#endif
-#ifndef CROSSCLR_FWD_PF
-#define CROSSCLR_FWD_PF 2
-#endif
-#ifndef CROSSCLR_FWD_SCHED
-#define CROSSCLR_FWD_SCHED 1
-#endif
 // forward: per k-step 2 reads feed 2 MFMAs
-#if defined(CROSSCLR_EMU) || CROSSCLR_FWD_SCHED == 0
+#ifdef CROSSCLR_EMU
 #define SCHED_PIPELINE_FWD(nsteps, pf) do {} while (0)
 #else
 #define SCHED_PIPELINE_FWD(nsteps, pf)                                                       \
@@ -319,7 +288,7 @@ __global__ void __launch_bounds__(256, 1) fast_bwd_kernel(const bf16_t* rows, co
     constexpr int QT = 32;                 // columns per tile
     constexpr int TILE = QT * RB;
     constexpr int NST = 4;                 // ring depth (power of two): one tile consumed, up to three in flight
-    constexpr int PF = (CROSSCLR_PF < DK / 2) ? CROSSCLR_PF : DK / 2;
+    constexpr int PF = (kFastPF < DK / 2) ? kFastPF : DK / 2;
     constexpr int DT = DK / 2;             // 32-wide output fragments
     CROSSCLR_SHARED __attribute__((aligned(16))) unsigned char lds[NST * TILE + NST * 128 * (SW ? 2 : 1)];
     unsigned char* stat = lds + NST * TILE;  // [NST][32] floats: 1/Z (or w/Z) of the tile's columns
@@ -390,41 +359,19 @@ __global__ void __launch_bounds__(256, 1) fast_bwd_kernel(const bf16_t* rows, co
     // ---- S^T = Xq . Xp^T : C[q][p], lane owns row p = l31 ----
     auto gemm1 = [&](const unsigned char* bt, const ColTile& ct) {
         f32x16 acc;
-        if (CROSSCLR_ABL & 4) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = bt[r] * 0.001f;
-            return acc;
-        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#if CROSSCLR_G1CHAINS == 2
-        f32x16 acc_odd;   // second accumulator chain: consecutive MFMAs independent
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc_odd[r] = 0.f;
-#endif
         bf16x8 ring[PF];
 #pragma unroll
         for (int i = 0; i < PF; ++i) ring[i] = *reinterpret_cast<const bf16x8*>(bt + off8[i & 7] + (i >> 3) * 256);
 #pragma unroll
         for (int ks = 0; ks < DK; ++ks) {
-            if (CROSSCLR_ABL & 32) {
-                acc = mfma_32x32x16_bf16(pf[(ks + 1) % DK], pf[ks], acc);
-                continue;
-            }
             const bf16x8 a_cur = ring[ks % PF];
             if (ks + PF < DK)
                 ring[ks % PF] = *reinterpret_cast<const bf16x8*>(bt + off8[(ks + PF) & 7] + ((ks + PF) >> 3) * 256);
-#if CROSSCLR_G1CHAINS == 2
-            if (ks & 1) acc_odd = mfma_32x32x16_bf16(a_cur, pf[ks], acc_odd);
-            else
-#endif
             acc = mfma_32x32x16_bf16(a_cur, pf[ks], acc);
         }
-        if (!(CROSSCLR_ABL & 32)) SCHED_PIPELINE(DK, 1, PF);
-#if CROSSCLR_G1CHAINS == 2
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] += acc_odd[r];
-#endif
+        SCHED_PIPELINE(DK, 1, PF);
         return acc;
     };
     // ---- W = s E (1/Z_p + 1/Z_q), packed to bf16: the A fragments of the second product ----
@@ -433,16 +380,14 @@ __global__ void __launch_bounds__(256, 1) fast_bwd_kernel(const bf16_t* rows, co
         const bool weighted = SW && same_mod;
         const float c2 = same_mod ? g.c_intra : g.c_inter;
         const float rzp = same_mod ? rzp_intra : rzp_inter;
-        if (!(CROSSCLR_ABL & 2)) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) x[r] = x[r] * c2 - g.m2;
-            // the intra-modal self pair is excluded (its exp(0) is added analytically by the forward):
-            // only on the one tile that holds the diagonal, send that scaled logit to -inf
-            if (same_mod && ct.rank == g.row_rank && ct.in_mod0 == (r_in_mod - l31)) {
+        for (int r = 0; r < 16; ++r) x[r] = x[r] * c2 - g.m2;
+        // the intra-modal self pair is excluded (its exp(0) is added analytically by the forward):
+        // only on the one tile that holds the diagonal, send that scaled logit to -inf
+        if (same_mod && ct.rank == g.row_rank && ct.in_mod0 == (r_in_mod - l31)) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (frag_row(r, half) == l31) x[r] = -__builtin_inff();
-            }
+            for (int r = 0; r < 16; ++r)
+                if (frag_row(r, half) == l31) x[r] = -__builtin_inff();
         }
 #pragma unroll
         for (int th = 0; th < 2; ++th) {
@@ -457,20 +402,13 @@ __global__ void __launch_bounds__(256, 1) fast_bwd_kernel(const bf16_t* rows, co
                 for (int j = 0; j < 4; ++j) {
                     const float v = x[8 * th + 4 * r4 + j];
                     const float zz = weighted ? (rzp * kq[j] + rq[j] * kp) : (rzp + rq[j]);
-                    pk.e[4 * r4 + j] = f32_to_bf16_bits((CROSSCLR_ABL & 2) ? v : fast_exp2(v) * zz);
+                    pk.e[4 * r4 + j] = f32_to_bf16_bits(fast_exp2(v) * zz);
                 }
             }
             af[th] = __builtin_bit_cast(bf16x8, pk);
         }
     };
     struct Pair { s16x4 lo, hi; };
-    auto trpair = [&](const unsigned char* bt, int tp, int dt) {
-        if (CROSSCLR_ABL & 16) return __builtin_bit_cast(Pair, pf[(2 * dt + tp) % DK]);
-        Pair p;
-        p.lo = lds_read_tr16_b64(bt + comb[dt & 3][0] + (16 * tp) * RB + 256 * (dt >> 2));
-        p.hi = lds_read_tr16_b64(bt + comb[dt & 3][1] + (16 * tp + 8) * RB + 256 * (dt >> 2));
-        return p;
-    };
 
     // ring of NST stages: tile t being consumed, t1 and t2 in flight
     t = next(t);
@@ -481,11 +419,9 @@ __global__ void __launch_bounds__(256, 1) fast_bwd_kernel(const bf16_t* rows, co
     int stage = 0;
     while (t < t_end) {
         const int t3 = next(t2 + 1);
-        if (!(CROSSCLR_ABL & 8)) {
-            wait_keep((t1 < t_end) + (t2 < t_end));   // tile t landed (its DMA was issued before t1's and t2's)
-            barrier_keep_dma();                         // ... everywhere; and every wave finished tile t-1
-            if (t3 < t_end) issue(t3, (stage + 3) & (NST - 1));
-        }
+        wait_keep((t1 < t_end) + (t2 < t_end));   // tile t landed (its DMA was issued before t1's and t2's)
+        barrier_keep_dma();                         // ... everywhere; and every wave finished tile t-1
+        if (t3 < t_end) issue(t3, (stage + 3) & (NST - 1));
         const unsigned char* bt = lds + stage * TILE;
         const ColTile ct = col_tile(g, tile_of(t), QT);
         const f32x16 acc = gemm1(bt, ct);
@@ -495,7 +431,7 @@ __global__ void __launch_bounds__(256, 1) fast_bwd_kernel(const bf16_t* rows, co
         // ---- G[p][:] += W[p][q] . Xq[q][:]  (contraction over the tile's 32 rows).  Item i = (k-step i / DT, output fragment
         // i % DT); B fragments by asm transpose reads PF items ahead of the fused {counted wait, MFMA} that consumes them
         // (the ds_read_tr BUILTIN drew a vmcnt(0) in front of every tile's second product: the whole DMA ring drained there)
-        if (!(CROSSCLR_ABL & 1)) {
+        {
             constexpr int NI = 2 * DT;
             constexpr int PF2 = PF < NI / 2 ? PF : NI / 2;
             const auto xa = lds_addr(bt);
@@ -572,7 +508,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) fast_bwd16_kernel(const bf16_
     constexpr int TILE = QT * RB;
     constexpr int NST = (4 * TILE + 512 <= 160 * 1024) ? 4 : 2;   // ring depth
     constexpr int DS = DP / 16;            // 16-wide output fragments
-    constexpr int PF = (CROSSCLR_PF < DKK / 2) ? CROSSCLR_PF : (DKK / 2 > 0 ? DKK / 2 : 1);
+    constexpr int PF = (kFastPF < DKK / 2) ? kFastPF : (DKK / 2 > 0 ? DKK / 2 : 1);
     constexpr int NOPS = QT * RB / 1024 / NW + 1 + (SW ? 1 : 0);
     CROSSCLR_SHARED __attribute__((aligned(16))) unsigned char lds[NST * TILE + NST * 128 * (SW ? 2 : 1)];
     unsigned char* stat = lds + NST * TILE;
@@ -645,11 +581,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) fast_bwd16_kernel(const bf16_
 #pragma unroll
         for (int k = 1; k < NST - 1; ++k) inflight += (tl[k] < t_end);
         wait_keep(inflight);
-#if CROSSCLR_TUNE & 4
-        __syncthreads();
-#else
         barrier_keep_dma();
-#endif
         if (tl[NST - 1] < t_end) issue(tl[NST - 1], (stage + NST - 1) % NST);
         const unsigned char* bt = lds + stage * TILE;
         const ColTile ct = col_tile(g, tile_of(tl[0]), QT);
@@ -714,7 +646,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) fast_bwd16_kernel(const bf16_
         // ---- G[p][:] += W[p][q] . Xq[q][:] : one k-step (32 columns) per 16-wide output fragment; B fragments by asm
         // transpose reads PF2 fragments ahead of their MFMA (the builtin form drained the DMA ring: see fast_bwd_kernel) ----
         {
-            constexpr int PF2 = CROSSCLR_PF < DS / 2 ? CROSSCLR_PF : DS / 2;
+            constexpr int PF2 = kFastPF < DS / 2 ? kFastPF : DS / 2;
             const auto xa = lds_addr(bt);
             decltype(lds_addr(bt)) base[8];
 #pragma unroll
@@ -732,7 +664,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) fast_bwd16_kernel(const bf16_
                 wait_lgkm<2 * later>(ring[ds % PF2].lo, ring[ds % PF2].hi);
                 acc2[ds] = mfma_16x16x32_bf16(af, __builtin_bit_cast(bf16x8, ring[ds % PF2]), acc2[ds]);
                 if constexpr (ds + PF2 < DS) fetch(IdxC<ds + PF2>{});
-                if (!(CROSSCLR_TUNE & 2)) sched_fence();
+                sched_fence();
             });
         }
 #pragma unroll
@@ -889,7 +821,6 @@ CROSSCLR_LEAF int fast_forward_pipe(const crossclr_plan* p, const Geo& g, const 
     dim3 grid(wk.nblk), block(256);
     const bool sw = krows != nullptr && kcols != nullptr;
     // XCD-aware placement of the ranges (crossclr_device.h: fwd_make_perm), computed once per work list and thread
-    static const bool xcd_aware = [] { const char* e = getenv("CROSSCLR_FWD_XCD"); return !(e && e[0] == '0'); }();
     static thread_local struct { FwdWork wk; FwdPerm perm; bool valid; } pcache[4];
     static thread_local int pnext = 0;
     const FwdPerm* permp = nullptr;
@@ -900,7 +831,7 @@ CROSSCLR_LEAF int fast_forward_pipe(const crossclr_plan* p, const Geo& g, const 
         pnext = (pnext + 1) & 3;
         memset(&e.wk, 0, sizeof(FwdWork));
         e.wk = wk;
-        fwd_make_perm(wk, xcd_aware, &e.perm);
+        fwd_make_perm(wk, true, &e.perm);
         e.valid = true;
         permp = &e.perm;
     }
@@ -1039,11 +970,6 @@ CROSSCLR_LEAF int launch_saved_xfp(const SavedLaunch& a) {
     const int accumulate = a.accumulate, tps2 = a.tps, mode = a.mode;
     (void)grid; (void)block; (void)stream; (void)st; (void)sb; (void)xfo; (void)rz; (void)wrz; (void)rz_cols; (void)wrz_cols; (void)kc; (void)gbuf;
     (void)accumulate; (void)tps2; (void)mode;
-#ifdef CROSSCLR_DSL_MINIMAL   // tuning builds (tools/build_variant.py): only the headline instantiation is compiled
-    if (p->Dpad != 512 || ks || mode != 0) return CROSSCLR_E_ARG;
-    CROSSCLR_FAST_LAUNCH((fast_bwd_xfp_kernel<32, false, 0, 1, 8>), grid, block, stream, xfo, st, sb, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps2, ks, kc);
-    return CROSSCLR_OK;
-#else
 #define CROSSCLR_LBP3(DK, SW, XP, TPRF, GRID)                                                                                                                                    \
     do {                                                                                                                                                                         \
         if (mode == 0) CROSSCLR_FAST_LAUNCH((fast_bwd_xfp_kernel<DK, SW, 0, XP, TPRF>), GRID, block, stream, xfo, st, sb, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps2, ks, kc);      \
@@ -1064,7 +990,6 @@ CROSSCLR_LEAF int launch_saved_xfp(const SavedLaunch& a) {
 #undef CROSSCLR_LBP
 #undef CROSSCLR_LBP3
     return CROSSCLR_OK;
-#endif
 }
 #endif   // CROSSCLR_DEF_SAVED_XFP
 
@@ -1084,11 +1009,6 @@ CROSSCLR_LEAF int launch_saved_xf1(const SavedLaunch& a) {
     float* gbuf = a.gbuf;
     const int accumulate = a.accumulate, tps = a.tps;
     (void)grid; (void)block; (void)stream; (void)c; (void)st; (void)rz; (void)wrz; (void)rz_cols; (void)wrz_cols; (void)kc; (void)gbuf; (void)accumulate; (void)tps;
-#ifdef CROSSCLR_DSL_MINIMAL
-    if (p->Dpad != 512 || ks) return CROSSCLR_E_ARG;
-    CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<32, false, 0, 1, 8, true>), grid, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc);
-    return CROSSCLR_OK;
-#else
 #define CROSSCLR_LBX2(DK) do { dim3 grid2(2 * p->bpad / 128, p->bwd_slices, 2);                                                                  \
                                if (ks) CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<DK, true, 0, 2, 4, true>), grid2, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc); \
                                else CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<DK, false, 0, 2, 4, true>), grid2, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc); } while (0)
@@ -1106,7 +1026,6 @@ CROSSCLR_LEAF int launch_saved_xf1(const SavedLaunch& a) {
 #undef CROSSCLR_LBX
 #undef CROSSCLR_LBX2
     return CROSSCLR_OK;
-#endif
 }
 #endif   // CROSSCLR_DEF_SAVED_XF1
 
@@ -1126,11 +1045,6 @@ CROSSCLR_LEAF int launch_saved_lds(const SavedLaunch& a) {
     float* gbuf = a.gbuf;
     const int accumulate = a.accumulate, tps = a.tps, mode = a.mode;
     (void)grid; (void)block; (void)stream; (void)c; (void)st; (void)rz; (void)wrz; (void)rz_cols; (void)wrz_cols; (void)kc; (void)gbuf; (void)accumulate; (void)tps; (void)mode;
-#ifdef CROSSCLR_DSL_MINIMAL
-    if (p->Dpad != 512 || ks || mode != 0) return CROSSCLR_E_ARG;
-    CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<32, false, 0>), grid, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc);
-    return CROSSCLR_OK;
-#else
 #define CROSSCLR_LB3(DK, SW, XP, TPRF, GRID)                                                                                                   \
     do {                                                                                                                                        \
         if (mode == 0) CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<DK, SW, 0, XP, TPRF>), GRID, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc);      \
@@ -1157,7 +1071,6 @@ CROSSCLR_LEAF int launch_saved_lds(const SavedLaunch& a) {
 #undef CROSSCLR_LB
 #undef CROSSCLR_LB3
     return CROSSCLR_OK;
-#endif
 }
 #endif   // CROSSCLR_DEF_SAVED_LDS
 
@@ -1181,9 +1094,6 @@ CROSSCLR_LEAF int launch_saved_wide(const SavedLaunch& a) {
     (void)block; (void)stream; (void)c; (void)st; (void)rz; (void)wrz; (void)rz_cols; (void)wrz_cols; (void)kc; (void)gbuf; (void)accumulate; (void)tps;
     const int mode = a.mode;
     if (mode != 0 && mode != 1) return CROSSCLR_E_ARG;       // (1: a rectangular block against other ranks' columns, crossclr_backward_rect_saved)
-#ifdef CROSSCLR_DSL_MINIMAL
-    return CROSSCLR_E_ARG;
-#else
 #define CROSSCLR_LBW2(DK, XP, SW) do { if (mode == 0) CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<DK, SW, 0, XP, 4>), gridw, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc); \
                                        else CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<DK, SW, 1, XP, 4>), gridw, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc); } while (0)
 #define CROSSCLR_LBW(DK, XP) do { dim3 gridw(2 * p->bpad / 128, p->bwd_slices, XP);                                                            \
@@ -1203,7 +1113,6 @@ CROSSCLR_LEAF int launch_saved_wide(const SavedLaunch& a) {
 #undef CROSSCLR_LBW
 #undef CROSSCLR_LBW2
     return CROSSCLR_OK;
-#endif
 }
 // the same on the fragment-major operand with the pair kernel (crossclr_kernels_dslp.h): what the module takes from 4096 padded rows on
 CROSSCLR_LEAF int launch_saved_wide_xfp(const SavedLaunch& a) {
@@ -1220,9 +1129,6 @@ CROSSCLR_LEAF int launch_saved_wide_xfp(const SavedLaunch& a) {
     const int accumulate = a.accumulate, tps2 = a.tps;
     (void)block; (void)stream; (void)st; (void)sb; (void)xfo; (void)rz; (void)wrz; (void)rz_cols; (void)wrz_cols; (void)kc; (void)gbuf; (void)accumulate; (void)tps2;
     if (a.mode != 0) return CROSSCLR_E_ARG;
-#ifdef CROSSCLR_DSL_MINIMAL
-    return CROSSCLR_E_ARG;
-#else
 #define CROSSCLR_LBWP(DK, XP) do { dim3 gridw(2 * p->bpad / 128, p->bwd_slices, XP);                                                            \
                                    if (ks) CROSSCLR_FAST_LAUNCH((fast_bwd_xfp_kernel<DK, true, 0, XP, 4>), gridw, block, stream, xfo, st, sb, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps2, ks, kc); \
                                    else CROSSCLR_FAST_LAUNCH((fast_bwd_xfp_kernel<DK, false, 0, XP, 4>), gridw, block, stream, xfo, st, sb, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps2, ks, kc); } while (0)
@@ -1240,7 +1146,6 @@ CROSSCLR_LEAF int launch_saved_wide_xfp(const SavedLaunch& a) {
     }
 #undef CROSSCLR_LBWP
     return CROSSCLR_OK;
-#endif
 }
 #endif   // CROSSCLR_DEF_SAVED_WIDE
 

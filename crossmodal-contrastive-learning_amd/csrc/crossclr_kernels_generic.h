@@ -654,6 +654,11 @@ __global__ void __launch_bounds__(256) rowmax_combine_kernel(const float* part, 
 //   kind 1/2/3: persistent fast forward (symmetric / rectangular / pairs): row block I owns slots
 //             0 .. last_block(I) - first_block(I) (fwdw_*: crossclr_device.h, per = cost units per thread block);
 //             kind 1 additionally has column sums colpart[I' < I][p]
+// LPR lanes per row: lane q of the group adds the terms k = q, q + LPR, ... (independent loads, fixed order), the group combines by a
+// butterfly.  4 lanes: 10 us at B = 8192; 16 lanes (a quarter of the loads per lane, four times the blocks and the fp64 logs): 13-15 us
+// (profiles/r05i_ab_finish_lpr.txt) -- the kernel is bound by its chain of dependent round trips (header -> sums -> log -> block sum),
+// not by the loads per lane.  (crossclr_api.cpp sizes the loss workspace by the same constant.)
+constexpr int kFinishLpr = 4;
 __global__ void __launch_bounds__(256) fwd_finish_kernel(const float* part, int nlaunch, int slots_per_launch, Geo g,
                                                          const float* diag_cos, float inv_tau, float neg_w, float* logz,
                                                          float* rz, float* wrz, double* loss_ws, const float* colpart,
@@ -663,14 +668,7 @@ __global__ void __launch_bounds__(256) fwd_finish_kernel(const float* part, int 
     CROSSCLR_SHARED int last_block;
     const int n = 2 * g.bpad;
     double acc = 0.0;
-    // LPR lanes per row: lane q of the group adds the terms k = q, q + LPR, ... (independent loads, fixed order), the group combines by a
-    // butterfly.  4 lanes: 10 us at B = 8192; 16 lanes (a quarter of the loads per lane, four times the blocks and the fp64 logs): 13-15 us
-    // (profiles/r05i_ab_finish_lpr.txt) -- the kernel is bound by its chain of dependent round trips (header -> sums -> log -> block sum),
-    // not by the loads per lane.
-#ifndef CROSSCLR_FINISH_LPR
-#define CROSSCLR_FINISH_LPR 4
-#endif
-    constexpr int LPR = CROSSCLR_FINISH_LPR;
+    constexpr int LPR = kFinishLpr;
     const int q = threadIdx.x & (LPR - 1);
     for (int p = (blockIdx.x * 256 + threadIdx.x) / LPR; p < n; p += gridDim.x * (256 / LPR)) {
         const int mod = p / g.bpad, i = p - mod * g.bpad;

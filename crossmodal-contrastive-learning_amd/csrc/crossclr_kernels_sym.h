@@ -112,15 +112,9 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pipe_kernel(const bf16_t* x, 
     }
     // (tiles past the end of the work list are clamped to the last column tile: a harmless re-fetch into a free stage that
     // keeps the VMEM count per iteration constant and the k-step chain free of branches)
-#ifndef CROSSCLR_YABL
-#define CROSSCLR_YABL 0   // timing ablations of this kernel (WRONG results): bit0 every block streams the same 64 column tiles (L2-resident),
-                          // bit1 no stash stores, bit2 no column-sum butterfly, bit3 plain epilogue for every tile (no overlap), bit4 no DMA,
-                          // bit5 no epilogue at all, bit6 no barrier, bit7 every second LDS read of the column tile skipped
-#endif
     const int mt_last = col_segs * per_rank - 1;
-    auto tile_of = [&](const Cursor& c) { return (CROSSCLR_YABL & 1) ? (c.mt & 63) : (c.mt < mt_last ? (c.mt < 0 ? 0 : c.mt) : mt_last); };
+    auto tile_of = [&](const Cursor& c) { return c.mt < mt_last ? (c.mt < 0 ? 0 : c.mt) : mt_last; };
     auto issue_piece = [&](const Cursor& c, int stage, int k) {
-        if (CROSSCLR_YABL & 16) return;
         lds_dma16_buf(rs_x, voffx[k], (unsigned)tile_of(c) * (unsigned)TILE, lds + stage * TILE + (wave + 4 * k) * 1024);
     };
     auto issue_stat = [&](const Cursor& c, int stage) {     // SW: the tile's 32 k_q (every wave issues it: equal VMEM counts)
@@ -190,7 +184,6 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pipe_kernel(const bf16_t* x, 
     };
     // general (masked / weighted) epilogue of one tile, not overlapped with anything
     auto epilogue_plain = [&](f32x16 (&acc)[NH], const Prev& pv) {
-        if (CROSSCLR_YABL & 32) { rowacc[0] += acc[0][0] + acc[NH - 1][1]; return; }
         const bool same_mod = pv.cmod == rmod;
         const float c2s = same_mod ? g.c_intra : g.c_inter;
         const bool upper = wants_colsum(pv.j);
@@ -273,7 +266,7 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pipe_kernel(const bf16_t* x, 
             wait_loads_visible();   // here, once per row block -- not as vmcnt countdowns inside every tile's MFMA stream
         }
         wait_dma_keep<(NST - 2) * NOPS>();   // tile w has landed (the NST-2 tiles issued after it may still be in flight) ...
-        if (!(CROSSCLR_YABL & 64)) barrier_keep_dma();   // ... everywhere; and every wave is done with tile w-1's stage
+        barrier_keep_dma();   // ... everywhere; and every wave is done with tile w-1's stage
         if (pending) { flush(); pending = false; }
         const int rstage = (stage + NST - 1) % NST;
         const auto xa = lds_addr(lds + stage * TILE);
@@ -289,7 +282,6 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pipe_kernel(const bf16_t* x, 
         u32x4 ring[PF];
         auto fetch = [&](auto ic) {
             constexpr int k = decltype(ic)::value;
-            if ((CROSSCLR_YABL & 128) && (k & 1)) { ring[k % PF] = ring[(k + PF - 1) % PF]; return; }   // (ablation: half the LDS reads)
             ring[k % PF] = lds_read_b128_async<(k >> 3) * 256>(abase[k & 7]);
         };
         // one k-step = two half-slots, each opened by an MFMA (NH == 2: one per row half; NH == 1: the second is empty): wait for
@@ -327,7 +319,6 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pipe_kernel(const bf16_t* x, 
             constexpr int H = 2 * DK, H1 = H / 2, H2 = 3 * H / 4;
             auto chore = [&](auto hc) {
                 constexpr int h = decltype(hc)::value;
-                if (CROSSCLR_YABL & 32) { if (h == 0) rowacc[0] += pacc[0][0] + pacc[NH - 1][1]; return; }   // (keeps the MFMAs alive)
                 if constexpr (h < H1) {
 #pragma unroll
                     for (int idx = (NE * h) / H1; idx < (NE * (h + 1)) / H1; ++idx) {
@@ -342,7 +333,7 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pipe_kernel(const bf16_t* x, 
 #pragma unroll
                         for (int r = (16 * i) / n; r < (16 * (i + 1)) / n; ++r) es[r] = NH == 2 ? e[0][r] + e[NH - 1][r] : e[0][r];
                     }
-                    if (ST && !(CROSSCLR_YABL & 2)) {
+                    if (ST) {
 #pragma unroll
                         for (int f = (2 * NH * i) / n; f < (2 * NH * (i + 1)) / n; ++f) {
                             const int s = f >> 1, th = f & 1;
@@ -358,7 +349,6 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pipe_kernel(const bf16_t* x, 
                     constexpr int lo = (16 * i) / n, hi = (16 * (i + 1)) / n;   // work units 0..7: k8, 8..11: k4, 12..13: k2, 14: k1, 15: publish
 #pragma unroll
                     for (int u = lo; u < hi; ++u) {
-                        if (CROSSCLR_YABL & 4) { if (u == 15) { k2[0] = es[l31 & 15]; } else continue; }
                         if (u < 8) {
                             const bool up = (l31 >> 3) & 1;
                             k8[u] = (up ? es[8 + u] : es[u]) + lane_xor<15>(up ? es[u] : es[8 + u]);
@@ -408,7 +398,7 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pipe_kernel(const bf16_t* x, 
             prev.valid = true;
             // fast = nothing to mask: KIND 1 tiles of the diagonal block (j < TPR) hold the self pairs; padding rows only matter
             // where column sums are formed
-            prev.fast = !SW && !ragged && !(colsum && padrows) && !(KIND == 1 && !colsum) && !selfpairs && !(CROSSCLR_YABL & 8);
+            prev.fast = !SW && !ragged && !(colsum && padrows) && !(KIND == 1 && !colsum) && !selfpairs;
             prev.crank = crank;
             prev.j = cq[0].j;
             prev.cmod = cmod;

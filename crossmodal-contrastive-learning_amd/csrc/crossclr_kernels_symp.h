@@ -32,33 +32,12 @@
 
 namespace crossclr {
 
-#ifndef CROSSCLR_ZABL
-#define CROSSCLR_ZABL 0   // timing ablations (WRONG results): bit0 no overlapped epilogue chores, bit1 no stash stores, bit2 no DMA,
-                          // bit3 no barrier, bit4 no MFMA, bit5 no fragment reads after the first tile, bit6 no butterfly
-#endif
-
-#ifndef CROSSCLR_ZPF
-#define CROSSCLR_ZPF 4    // A fragments in flight ahead of their MFMA pair (k-steps); the first ZPF fragments of a tile are read during the previous tile
-#endif
-#ifndef CROSSCLR_ZW
-#define CROSSCLR_ZW 2     // k-steps per counted LDS wait (2: one wait covers the fragments of k-steps k and k + 1; 1: a wait per k-step)
-#endif
-#ifndef CROSSCLR_ZKB
-#define CROSSCLR_ZKB -1   // the k-step in front of which the tile's barrier sits (even; -1: DK / 2).  Measured (profiles/r05c_ab_fwdp.txt): the barrier
-                          // at k-step 2 with the DMA pieces spread over every second k-step behind it is not faster (0.130 vs 0.127 ms without save)
-#endif
-#ifndef CROSSCLR_ZLAG
-#define CROSSCLR_ZLAG 1   // column-sum butterfly: the DPP add of unit u - 1 behind the selects of unit u (no s_nop between a select and its DPP reader)
-#endif
-
 #ifndef CROSSCLR_EMU
 // accumulators in VGPRs (the epilogue reads them with plain VALU), B fragments in AGPRs (256 of them: the whole accumulation-register half)
 __device__ __forceinline__ void mfma_first_va(f32x16& acc, bf16x8 a, bf16x8 b) {
-    if (CROSSCLR_ZABL & 16) { asm volatile("" : "=v"(acc) : "v"(a), "a"(b)); return; }
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "a"(b));
 }
 __device__ __forceinline__ void mfma_va(f32x16& acc, bf16x8 a, bf16x8 b) {
-    if (CROSSCLR_ZABL & 16) { asm volatile("" : "+v"(acc) : "v"(a), "a"(b)); return; }
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(b));
 }
 // a finished accumulator may be read by VALU 19 wait states after the MFMA that wrote it (16-pass XDL write -> VALU read); the asm MFMAs are
@@ -95,8 +74,10 @@ template <int OFF0, int OFF1> __device__ __forceinline__ u32x2 lds_read2_b32_asy
 // Read q = 0 .. DK-1 of a step: q < DK - PF fetches the A fragment of k-step q + PF of THIS tile, the last PF ones the fragments of k-steps
 // 0 .. PF-1 of the NEXT tile.  One read per k-step up to k-step DK - 9, two per k-step in k-steps DK - 8 .. DK - 5, none in the last four.
 struct FwdReadPlan {
-    static constexpr int PF = CROSSCLR_ZPF;
-    static constexpr int kb(int DK) { return CROSSCLR_ZKB < 0 ? DK / 2 : CROSSCLR_ZKB; }
+    static constexpr int PF = 4;      // A fragments in flight ahead of their MFMA pair (k-steps); the first PF fragments of a tile are read during the previous tile
+    // the k-step in front of which the tile's barrier sits.  Measured (profiles/r05c_ab_fwdp.txt): the barrier at k-step 2 with the DMA
+    // pieces spread over every second k-step behind it is not faster (0.130 vs 0.127 ms without save)
+    static constexpr int kb(int DK) { return DK / 2; }
     static constexpr int kstep_of(int DK, int q) { return q < DK - 8 ? q : (DK - 8) + (q - (DK - 8)) / 2; }
     static constexpr int reads_before(int DK, int k) {        // reads issued in k-steps < k
         return k <= DK - 8 ? k : ((DK - 8) + 2 * (k - (DK - 8)) < DK ? (DK - 8) + 2 * (k - (DK - 8)) : DK);
@@ -243,7 +224,6 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pair_kernel(const bf16_t* x, 
         }
     };
     auto issue_piece = [&](int k, unsigned tile_off, unsigned stage_off) {
-        if (CROSSCLR_ZABL & 4) return;
         lds_dma16_buf(rs_x, voffx[k], tile_off, lds + stage_off + (wave + 4 * k) * 1024);
     };
     // prologue: the first three stages of the range (KS = 1: the tiles of items w, w + 1, w + 2)
@@ -292,7 +272,7 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pair_kernel(const bf16_t* x, 
         pend_soff = soff;
     };
     auto stash_store = [&](const f32x16& e, int s, unsigned soff) {
-        if (!ST || (CROSSCLR_ZABL & 2)) return;
+        if (!ST) return;
 #pragma unroll
         for (int th = 0; th < 2; ++th) {
             Bits8 pk;
@@ -363,7 +343,7 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pair_kernel(const bf16_t* x, 
     // ---- one stage: NH DK MFMAs into accC (stage KH of tile jt); MODE 1: the epilogue of the previous tile (accP, index jt - 1) in their shadow ----
     auto step = [&](auto modec, auto khc, f32x16 (&accC)[NH], f32x16 (&accP)[NH], int jt) __attribute__((always_inline)) {
         constexpr int MODE = decltype(modec)::value, KH = decltype(khc)::value;
-        constexpr bool EPI = MODE == 1 && !(CROSSCLR_ZABL & 1);
+        constexpr bool EPI = MODE == 1;
         const unsigned nstage = ring_next(cstage);
         const int ring_step = (int)nstage - (int)cstage;      // + TILE, or back to the first stage
         decltype(lds_addr(lds)) anext[PF];
@@ -397,10 +377,6 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pair_kernel(const bf16_t* x, 
 
         auto issue_read = [&](auto qc) {
             constexpr int q = decltype(qc)::value;
-            if ((CROSSCLR_ZABL & 32)) {
-                if constexpr (q < DK - PF) fr[q + PF] = fr[(q + PF) % PF]; else nn[q - (DK - PF)] = fr[q - (DK - PF)];
-                return;
-            }
             if constexpr (q < DK - PF) {
                 constexpr int kf = q + PF;
                 fr[kf] = lds_read_b128_async<(kf >> 3) * 256>(abase[kf & 7]);
@@ -440,7 +416,7 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pair_kernel(const bf16_t* x, 
                         else es[r] = NH == 2 ? accP[0][r] + accP[NH - 1][r] : accP[0][r];
                     }
                 }
-                if (ST && !(CROSSCLR_ZABL & 2)) {
+                if (ST) {
 #pragma unroll
                     for (int f = (2 * NH * i) / n; f < (2 * NH * (i + 1)) / n; ++f) {
                         const int s = f >> 1, th = f & 1;
@@ -452,29 +428,6 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pair_kernel(const bf16_t* x, 
                 }
             } else if constexpr (!CSUM) {
                 // (rectangular launch without column sums: the last quarter of the tile carries no chores)
-            } else if constexpr (CROSSCLR_ZLAG == 0) {
-                constexpr int n = H - H2, i = h - H2;
-                constexpr int lo = (16 * i) / n, hi = (16 * (i + 1)) / n;     // units 0..7: k8, 8..11: k4, 12..13: k2, 14: k1, 15: (publish: behind the loop)
-#pragma unroll
-                for (int u = lo; u < hi; ++u) {
-                    if (CROSSCLR_ZABL & 64) { if (u == 14) k2[0] = es[l31 & 15]; continue; }
-                    if (u < 8) {
-                        const bool up = (l31 >> 3) & 1;
-                        k8[u] = (up ? es[8 + u] : es[u]) + lane_xor<15>(up ? es[u] : es[8 + u]);
-                    } else if (u < 12) {
-                        const int q = u - 8;
-                        const bool up = (l31 >> 2) & 1;
-                        k4[q] = (up ? k8[4 + q] : k8[q]) + lane_xor<7>(up ? k8[q] : k8[4 + q]);
-                    } else if (u < 14) {
-                        const int q = u - 12;
-                        const bool up = (l31 >> 1) & 1;
-                        k2[q] = (up ? k4[2 + q] : k4[q]) + lane_xor<2>(up ? k4[q] : k4[2 + q]);
-                    } else if (u == 14) {
-                        const bool up = l31 & 1;
-                        const float k1 = (up ? k2[1] : k2[0]) + lane_xor<1>(up ? k2[0] : k2[1]);
-                        k2[0] = k1 + lane_xor<16>(k1);
-                    }
-                }
             } else {
                 // the same 15 exchanges (halving_sum16), each cut in two: unit u SELECTS its two operands, the DPP add that consumes them
                 // runs with unit u + 1 -- one MFMA slot later, so no wait states between a v_cndmask and the DPP instruction reading it
@@ -482,7 +435,6 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pair_kernel(const bf16_t* x, 
                 constexpr int lo = (16 * i) / n, hi = (16 * (i + 1)) / n;
 #pragma unroll
                 for (int u = lo; u < hi; ++u) {
-                    if (CROSSCLR_ZABL & 64) { if (u == 15) k2[0] = es[l31 & 15]; continue; }
                     // combine(u - 1)
                     if (u >= 1 && u <= 8) k8[u - 1] = sa[u - 1] + lane_xor<15>(sb[u - 1]);
                     else if (u >= 9 && u <= 12) k4[u - 9] = sa[u - 1] + lane_xor<7>(sb[u - 1]);
@@ -522,9 +474,9 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pair_kernel(const bf16_t* x, 
         static_for<DK>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
             // ---- head: the fragments of k-steps k and k + 1 are complete (one counted wait per two k-steps); at k-step KB + 2 the flush's reads too
-            if constexpr ((k >= PF && (k % CROSSCLR_ZW == 0)) || k == KB + 2) {
-                constexpr bool frag = k >= PF && (k % CROSSCLR_ZW == 0);
-                constexpr int kl = (CROSSCLR_ZW == 2 && k + 1 < DK) ? k + 1 : k;
+            if constexpr ((k >= PF && k % 2 == 0) || k == KB + 2) {
+                constexpr bool frag = k >= PF && k % 2 == 0;
+                constexpr int kl = k + 1 < DK ? k + 1 : k;
                 constexpr int keep_frag = frag ? FwdReadPlan::keep_for(DK, k, kl) : 63;
                 constexpr int keep_flush = k == KB + 2 ? FwdReadPlan::ops_before(DK, k) - FwdReadPlan::flush_seq(DK) - 1 : 63;
                 constexpr int keep = keep_flush < keep_frag ? keep_flush : keep_frag;
@@ -532,14 +484,14 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pair_kernel(const bf16_t* x, 
                 wait_lgkm_n<keep>();
                 if constexpr (frag) {
                     after_wait(fr[k]);
-                    if constexpr (CROSSCLR_ZW == 2 && k + 1 < DK) after_wait(fr[k + 1]);
+                    if constexpr (k + 1 < DK) after_wait(fr[k + 1]);
                 }
                 if constexpr (k == KB + 2) { after_wait(f01); after_wait(f23); }
             }
             if constexpr (k == KB) {
                 // tile i + 1 has landed (only the NXO pieces of tile i + 2 may still be in flight) -- everywhere; everybody is done with tile i - 1
-                if (!(CROSSCLR_ZABL & 4)) wait_dma_keep<NXO>();
-                if (!(CROSSCLR_ZABL & 8)) barrier_only();
+                wait_dma_keep<NXO>();
+                barrier_only();
                 f01 = lds_read2_b32_async<0, QT>(fa);
                 f23 = lds_read2_b32_async<2 * QT, 3 * QT>(fa);
                 if constexpr (SW && KH == 0) {       // this tile's column scales: IN FRONT of the step's DMA pieces (the closing vmcnt(NXO) covers them)
@@ -586,11 +538,7 @@ __global__ void __launch_bounds__(256, 1) fast_fwd_pair_kernel(const bf16_t* x, 
             for (int q = 0; q < 4; ++q) kq_next[q] = kqn[q];
         }
         pend = 0;
-        if constexpr (EPI && CSUM && KH == KS - 1) {
-            if (!(CROSSCLR_ZABL & 64)) publish(k2[0], ti.cs_off);
-        } else if constexpr (!EPI && MODE == 1 && KH == KS - 1) {
-            rowacc[0] += accP[0][0] + accP[NH - 1][1];      // (ablation: keeps the previous tile's MFMAs alive)
-        }
+        if constexpr (EPI && CSUM && KH == KS - 1) publish(k2[0], ti.cs_off);
         dma_advance();
         cstage = nstage;
 #pragma unroll

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""HIP-event time of crossclr_backward_saved_xfp (and _xf beside it) at B = 8192, D = 512 for the library CROSSCLR_HIP_LIBRARY names
-(ablation variants produce wrong results: timing only).  usage: time_xfp.py [label]"""
+"""HIP-event time of crossclr_backward_saved_xfp (and _xf beside it) at B = 8192, D = 512 for the library CROSSCLR_HIP_LIBRARY names.
+usage: time_xfp.py [label]"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, crossclr_amd

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Block timeline of the two pipelined kernels (BASELINE config 3 by default): when each of the 256 blocks starts, has its first tile,
 leaves its main loop and exits, and the shader clock the launch ran at.  Needs a library built with -DCROSSCLR_TIMING:
-    python tools/build_variant.py tm -DCROSSCLR_TIMING -DCROSSCLR_DSL_MINIMAL
+    python tools/build_variant.py tm -DCROSSCLR_TIMING
     CROSSCLR_HIP_LIBRARY=variants/libtm.so python tools/timeline.py [B] [D]
 The marks are s_memrealtime (100 MHz, one counter for the whole device) -> 10 ns resolution."""
 import ctypes, os, sys
