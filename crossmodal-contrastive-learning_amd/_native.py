@@ -16,10 +16,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # sources (tools/build_variant.py) for A/B timing.  It must still be a "hip-gfx950" library.
 HIP_LIBRARY = os.environ.get("CROSSCLR_HIP_LIBRARY", os.path.join(_HERE, "libcrossclr_hip.so"))
 
-MODE_FP32, MODE_BF16 = 0, 1
+MODE_FP32, MODE_BF16, MODE_BF16X3 = 0, 1, 2
 IN_F32, IN_F16, IN_BF16, IN_F64 = 0, 1, 2, 3
 E_RANGE = -2
-ABI_VERSION = 7
+ABI_VERSION = 8
 LAUNCH_GROUPS = 8      # CROSSCLR_LAUNCH_GROUPS of include/crossclr.h
 
 

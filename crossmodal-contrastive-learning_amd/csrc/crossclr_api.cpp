@@ -16,6 +16,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 #ifndef CROSSCLR_DEFAULT_BWD_KERNEL
 #define CROSSCLR_DEFAULT_BWD_KERNEL 1   // 1: 32-row waves, 2: 16-row waves (for Dpad <= 512, where both exist)
@@ -42,7 +43,8 @@ void note_kernel(int which, const char* name) { g_last_kernel[which & 1] = name;
 }  // namespace crossclr
 static void note_generic_launch(const char* what) {      // (the generic kernels are launched from this file: their launch_status label names them)
     if (!strncmp(what, "fwd_sums_kernel", 15)) crossclr::note_kernel(0, what);
-    else if (!strncmp(what, "bwd_kernel", 10) || !strncmp(what, "bwd_saved32_kernel", 18)) crossclr::note_kernel(1, what);
+    else if (!strncmp(what, "bwd_kernel", 10) || !strncmp(what, "bwd_saved32_kernel", 18) || !strncmp(what, "bwd_saved_x3_kernel", 19))
+        crossclr::note_kernel(1, what);
 }
 
 #ifdef CROSSCLR_EMU
@@ -71,6 +73,13 @@ extern "C" const char* crossclr_backend(void) {
 }
 
 static int round_up(int x, int m) { return (x + m - 1) / m * m; }
+// CROSSCLR_MODE_BF16X3 (include/crossclr.h): the generic kernels of the fp32 mode on the split operand (x3_t)
+static bool is_x3(const crossclr_plan* p) { return p->mode == CROSSCLR_MODE_BF16X3; }
+static int refuse_x3(const char* what) {
+    return fail(CROSSCLR_E_ARG, "%s: CROSSCLR_MODE_BF16X3 plans are not supported here (single-device loss step only)", what);
+}
+// label of a generic launch (crossclr_last_kernel): the split-operand instantiations carry <x3_t>
+template <typename T> static const char* glabel(const char* plain, const char* x3) { return std::is_same<T, x3_t>::value ? x3 : plain; }
 static const float* const kNoF = nullptr;     // (kernel arguments a launch does not use)
 
 // tuning knobs from the environment, read ONCE per process (not per call: crossclr_make_plan sits on the step's host path)
@@ -144,7 +153,9 @@ extern "C" int crossclr_make_plan(int b, int D, int world, int rank, int mode, c
     if (!plan) return fail(CROSSCLR_E_ARG, "plan is NULL");
     if (b < 1 || D < 1) return fail(CROSSCLR_E_ARG, "need b >= 1 and D >= 1 (got b=%d D=%d)", b, D);
     if (world < 1 || rank < 0 || rank >= world) return fail(CROSSCLR_E_ARG, "bad world/rank %d/%d", world, rank);
-    if (mode != CROSSCLR_MODE_FP32 && mode != CROSSCLR_MODE_BF16) return fail(CROSSCLR_E_ARG, "bad mode %d", mode);
+    if (mode != CROSSCLR_MODE_FP32 && mode != CROSSCLR_MODE_BF16 && mode != CROSSCLR_MODE_BF16X3) return fail(CROSSCLR_E_ARG, "bad mode %d", mode);
+    if (mode == CROSSCLR_MODE_BF16X3 && world != 1)
+        return fail(CROSSCLR_E_ARG, "CROSSCLR_MODE_BF16X3 is single-device: world must be 1 (got %d)", world);
     // the forward's flat work list, the stash and the column-sum workspace are indexed with 32-bit integers:
     // (2b/128 row blocks) x (2B/32 column tiles) must stay below 2^31 (whichever kernel the plan ends up with)
     {
@@ -249,7 +260,7 @@ extern "C" int crossclr_make_plan(int b, int D, int world, int rank, int mode, c
         plan->loss_ws_doubles = 1 + nb;
     }
     plan->fwd_ws_floats = ws_flag_off(plan) + 4 * kLaunchGroups;   // + the launch groups' headers
-    const size_t esz = mode == CROSSCLR_MODE_FP32 ? 4 : 2;
+    const size_t esz = mode == CROSSCLR_MODE_BF16 ? 2 : 4;      // (BF16X3: hi and lo)
     plan->operand_bytes = (size_t)2 * plan->bpad * plan->Dpad * esz;
     plan->gbuf_bytes = (size_t)plan->bwd_slices * 2 * plan->bpad * plan->Dpad * 4;
     plan->stash_bytes = 0;
@@ -257,8 +268,8 @@ extern "C" int crossclr_make_plan(int b, int D, int world, int rank, int mode, c
     if (plan->fast_path && plan->fast_bwd && !env.disable_save) plan->stash_bytes = fast_stash_bytes(plan->bpad, plan->Dpad);
     if (wide) plan->stash_bytes = wide_stash_bytes(plan->bpad);
     if (wide && plan->stash_bytes && !env.disable_xf && plan->operand_bytes < ((size_t)1 << 32)) plan->xf_bytes = plan->operand_bytes;
-    // exact-fp32 mode: the whole stacked [2 bpad] x [2 bpad] matrix of fp32 exponentials (1 GiB at b = 8192), up to 16 GiB
-    if (mode == CROSSCLR_MODE_FP32 && !env.disable_save && plan->operand_bytes < (1ull << 32)) {
+    // exact-fp32 mode (and BF16X3, the same stash): the whole stacked [2 bpad] x [2 bpad] matrix of fp32 exponentials (1 GiB at b = 8192), up to 16 GiB
+    if ((mode == CROSSCLR_MODE_FP32 || mode == CROSSCLR_MODE_BF16X3) && !env.disable_save && plan->operand_bytes < (1ull << 32)) {
         const size_t sb = (size_t)2 * plan->bpad * (size_t)2 * plan->bpad * 4;
         if (sb <= ((size_t)16 << 30)) plan->stash_bytes = sb;
     }
@@ -314,6 +325,9 @@ static int normalize_t(const crossclr_plan* p, const void* v, const void* t, lon
     if (p->mode == CROSSCLR_MODE_FP32)
         LAUNCH((normalize_kernel<TIN, float, NORM>), grid, block, stream, (const TIN*)v, (const TIN*)t, ldv, ldt, g,
                (float*)xhat, inv_norm, diag, zero_word);
+    else if (is_x3(p))
+        LAUNCH((normalize_kernel<TIN, x3_t, NORM>), grid, block, stream, (const TIN*)v, (const TIN*)t, ldv, ldt, g,
+               (x3_t*)xhat, inv_norm, diag, zero_word);
     else
         LAUNCH((normalize_kernel<TIN, bf16_t, NORM>), grid, block, stream, (const TIN*)v, (const TIN*)t, ldv, ldt, g,
                (bf16_t*)xhat, inv_norm, diag, zero_word);
@@ -553,16 +567,16 @@ static int forward_generic_sym(const crossclr_plan* plan, const Geo& g, const vo
             if (k) CROSSCLR_LSY(bf16_t, true, 0, true); else CROSSCLR_LSY(bf16_t, false, 0, true);
             return launch_status("fwd_sums_kernel (symmetric, save, bf16 records)");
         } else {
-            if (shift) { if (k) CROSSCLR_LSY(float, true, 2, true); else CROSSCLR_LSY(float, false, 2, true); }
-            else { if (k) CROSSCLR_LSY(float, true, 0, true); else CROSSCLR_LSY(float, false, 0, true); }
-            return launch_status("fwd_sums_kernel (symmetric, save)");
+            if (shift) { if (k) CROSSCLR_LSY(T, true, 2, true); else CROSSCLR_LSY(T, false, 2, true); }
+            else { if (k) CROSSCLR_LSY(T, true, 0, true); else CROSSCLR_LSY(T, false, 0, true); }
+            return launch_status(glabel<T>("fwd_sums_kernel (symmetric, save)", "fwd_sums_kernel<x3_t> (symmetric, save)"));
         }
     }
     if (rowmax) { if (k) CROSSCLR_LSY(T, true, 1, false); else CROSSCLR_LSY(T, false, 1, false); }
     else if (shift) { if (k) CROSSCLR_LSY(T, true, 2, false); else CROSSCLR_LSY(T, false, 2, false); }
     else { if (k) CROSSCLR_LSY(T, true, 0, false); else CROSSCLR_LSY(T, false, 0, false); }
 #undef CROSSCLR_LSY
-    return launch_status("fwd_sums_kernel (symmetric)");
+    return launch_status(glabel<T>("fwd_sums_kernel (symmetric)", "fwd_sums_kernel<x3_t> (symmetric)"));
 }
 
 static int forward_generic(const crossclr_plan* plan, const Geo& g, const void* rows, const void* cols, float* out,
@@ -585,14 +599,22 @@ static int forward_generic(const crossclr_plan* plan, const Geo& g, const void* 
     }
     if (stash) {   // exact-fp32 forward that also saves its exponentials (local block; common shift, or per-row shifts: mode 2)
         dim3 block(256);
-#define CROSSCLR_LSV(SW, MODE) LAUNCH((fwd_sums_kernel<float, SW, MODE, true>), grid, block, stream, (const float*)rows, (const float*)cols, g, tps, out, kcols, shift, stash, (int*)nullptr, const_cast<float*>(mode == 2 ? shift_cols : nullptr))
-        if (mode == 2) { if (kcols) CROSSCLR_LSV(true, 2); else CROSSCLR_LSV(false, 2); }
-        else { if (kcols) CROSSCLR_LSV(true, 0); else CROSSCLR_LSV(false, 0); }
+#define CROSSCLR_LSV(TT, SW, MODE) LAUNCH((fwd_sums_kernel<TT, SW, MODE, true>), grid, block, stream, (const TT*)rows, (const TT*)cols, g, tps, out, kcols, shift, stash, (int*)nullptr, const_cast<float*>(mode == 2 ? shift_cols : nullptr))
+        if (is_x3(plan)) {   // split operand, the same fp32 stash
+            if (mode == 2) { if (kcols) CROSSCLR_LSV(x3_t, true, 2); else CROSSCLR_LSV(x3_t, false, 2); }
+            else { if (kcols) CROSSCLR_LSV(x3_t, true, 0); else CROSSCLR_LSV(x3_t, false, 0); }
+            return launch_status("fwd_sums_kernel<x3_t> (save)");
+        }
+        if (mode == 2) { if (kcols) CROSSCLR_LSV(float, true, 2); else CROSSCLR_LSV(float, false, 2); }
+        else { if (kcols) CROSSCLR_LSV(float, true, 0); else CROSSCLR_LSV(float, false, 0); }
 #undef CROSSCLR_LSV
         return launch_status("fwd_sums_kernel (save)");
     }
     if (plan->mode == CROSSCLR_MODE_FP32) forward_generic_t<float>(plan, g, rows, cols, out, kcols, shift, mode, tps, grid, stream);
-    else forward_generic_t<bf16_t>(plan, g, rows, cols, out, kcols, shift, mode, tps, grid, stream);
+    else if (is_x3(plan)) {
+        forward_generic_t<x3_t>(plan, g, rows, cols, out, kcols, shift, mode, tps, grid, stream);
+        return launch_status("fwd_sums_kernel<x3_t>");
+    } else forward_generic_t<bf16_t>(plan, g, rows, cols, out, kcols, shift, mode, tps, grid, stream);
     return launch_status("fwd_sums_kernel");
 }
 
@@ -638,6 +660,7 @@ extern "C" int crossclr_forward_w(const crossclr_plan* plan, const void* xhat_ro
         !env_knobs().disable_symmetric) {
         // the local block (single device, or the local block of a sharded run), forward only: upper triangle + column sums
         float* colpart = part + ws_colpart_off(plan);
+        if (is_x3(plan)) return forward_generic_sym<x3_t>(plan, g, xhat_rows, out, kcols, colpart, header, stream);
         return plan->mode == CROSSCLR_MODE_FP32 ? forward_generic_sym<float>(plan, g, xhat_rows, out, kcols, colpart, header, stream)
                                                 : forward_generic_sym<bf16_t>(plan, g, xhat_rows, out, kcols, colpart, header, stream);
     }
@@ -665,9 +688,10 @@ extern "C" int crossclr_forward_save(const crossclr_plan* plan, const void* xhat
     int* header = reinterpret_cast<int*>(part + ws_flag_off(plan)) + 4 * (slot0 / plan->fwd_slots);
     if (!plan->fast_path && plan->mode == CROSSCLR_MODE_BF16)   // wide bf16 plan: upper triangle, bf16 records in the register-resident layout
         return forward_generic_sym<bf16_t>(plan, g, xhat, out, kcols, part + ws_colpart_off(plan), header, stream, static_cast<float*>(stash));
-    if (!plan->fast_path) {   // exact-fp32 mode
+    if (!plan->fast_path) {   // exact-fp32 mode (and BF16X3: the same launch on the split operand)
         if (!env_knobs().disable_symmetric)   // upper triangle; every fragment stored twice (as evaluated + transposed)
-            return forward_generic_sym<float>(plan, g, xhat, out, kcols, part + ws_colpart_off(plan), header, stream, static_cast<float*>(stash));
+            return is_x3(plan) ? forward_generic_sym<x3_t>(plan, g, xhat, out, kcols, part + ws_colpart_off(plan), header, stream, static_cast<float*>(stash))
+                               : forward_generic_sym<float>(plan, g, xhat, out, kcols, part + ws_colpart_off(plan), header, stream, static_cast<float*>(stash));
         rc = device_zero_header(header, stream);
         if (rc) return rc;
         return forward_generic(plan, g, xhat, xhat, out, kcols, nullptr, 0, stream, static_cast<float*>(stash));
@@ -676,6 +700,30 @@ extern "C" int crossclr_forward_save(const crossclr_plan* plan, const void* xhat
     return rc ? fail(rc, "fast_forward_save: unsupported Dpad %d", plan->Dpad) : launch_status("fast_fwd_kernel (save)");
 #endif
 }
+
+#ifndef CROSSCLR_NO_FAST
+// BF16X3 plans: the saved backward on the split operand (crossclr_kernels_saved32.h), single pass (RM = false) or two-pass (RM = true)
+template <bool RM>
+static int backward_saved_x3(const crossclr_plan* plan, const Geo& g, const void* xhat, const void* stash, const float* rz, const float* wrz,
+                             const float* k, float* gbuf, int accumulate, void* stream) {
+    const int NQ = 2 * plan->bpad / 32;
+    const int tps = (NQ + plan->bwd_slices - 1) / plan->bwd_slices;
+    const unsigned rb = 2 * plan->bpad / 64, nz = (unsigned)plan->bwd_slices;
+    dim3 block(256);
+#define CROSSCLR_LSX3(DC)                                                                                                                \
+    do {                                                                                                                                 \
+        if (k) LAUNCH((bwd_saved_x3_kernel<DC, true, RM>), dim3(rb, plan->Dpad / DC, nz), block, stream, (const x3_t*)xhat,             \
+                      (const float*)stash, g, rz, wrz, gbuf, accumulate, tps, k);                                                        \
+        else LAUNCH((bwd_saved_x3_kernel<DC, false, RM>), dim3(rb, plan->Dpad / DC, nz), block, stream, (const x3_t*)xhat,              \
+                    (const float*)stash, g, rz, wrz, gbuf, accumulate, tps, k);                                                          \
+    } while (0)
+    if (plan->Dpad % 256 == 0) CROSSCLR_LSX3(256);
+    else if (plan->Dpad % 128 == 0) CROSSCLR_LSX3(128);
+    else CROSSCLR_LSX3(64);
+#undef CROSSCLR_LSX3
+    return launch_status(RM ? "bwd_saved_x3_kernel (two-pass)" : "bwd_saved_x3_kernel");
+}
+#endif
 
 extern "C" int crossclr_backward_saved(const crossclr_plan* plan, const void* xhat, const void* stash, float temperature,
                                        float negative_weight, const float* rz, const float* wrz,
@@ -691,6 +739,7 @@ extern "C" int crossclr_backward_saved(const crossclr_plan* plan, const void* xh
     Geo g;
     int rc = make_geo(plan, 1, plan->rank, -1, temperature, negative_weight, &g);
     if (rc) return rc;
+    if (is_x3(plan)) return backward_saved_x3<false>(plan, g, xhat, stash, rz, wrz, krows, gbuf, accumulate, stream);
     if (!plan->fast_path && plan->mode == CROSSCLR_MODE_FP32) {   // exact-fp32 mode
         const int NQ = 2 * plan->bpad / 32;
         const int tps = (NQ + plan->bwd_slices - 1) / plan->bwd_slices;
@@ -877,7 +926,8 @@ extern "C" int crossclr_forward_rowmax(const crossclr_plan* plan, const void* xh
              !env_knobs().disable_symmetric) {   // the local block: upper triangle, column maxima for the mirrored tiles
         float* cp = part + ws_colpart_off(plan);
         int* header = reinterpret_cast<int*>(part + ws_flag_off(plan));   // (launch group 0's header: rewritten by the pass that follows)
-        rc = plan->mode == CROSSCLR_MODE_FP32 ? forward_generic_sym<float>(plan, g, xhat_rows, part, kcols, cp, header, stream, nullptr, nullptr, true)
+        rc = is_x3(plan) ? forward_generic_sym<x3_t>(plan, g, xhat_rows, part, kcols, cp, header, stream, nullptr, nullptr, true)
+           : plan->mode == CROSSCLR_MODE_FP32 ? forward_generic_sym<float>(plan, g, xhat_rows, part, kcols, cp, header, stream, nullptr, nullptr, true)
                                               : forward_generic_sym<bf16_t>(plan, g, xhat_rows, part, kcols, cp, header, stream, nullptr, nullptr, true);
         if (rc) return rc;
         colpart = cp;
@@ -909,6 +959,7 @@ extern "C" int crossclr_forward_s(const crossclr_plan* plan, const void* xhat_ro
     if (xhat_rows == xhat_cols && col_ranks == 1 && col_rank0 == plan->rank && skip_rank < 0 && krows == kcols &&
         !env_knobs().disable_symmetric) {   // the local block: upper triangle + column sums (two exponentials per element)
         float* colpart = part + ws_colpart_off(plan);
+        if (is_x3(plan)) return forward_generic_sym<x3_t>(plan, g, xhat_rows, out, kcols, colpart, header, stream, nullptr, shift_rows);
         return plan->mode == CROSSCLR_MODE_FP32
                    ? forward_generic_sym<float>(plan, g, xhat_rows, out, kcols, colpart, header, stream, nullptr, shift_rows)
                    : forward_generic_sym<bf16_t>(plan, g, xhat_rows, out, kcols, colpart, header, stream, nullptr, shift_rows);
@@ -938,7 +989,7 @@ static size_t stash_bytes_s(const crossclr_plan* plan) {
         const size_t rb = rect_bytes_s(plan);
         return rb ? (wide_two_pass(plan) ? 2 : 1) * rb + (size_t)2 * plan->bpad * 4 : 0;
     }
-    if (plan->fast_path || plan->mode != CROSSCLR_MODE_FP32) return 0;
+    if (plan->fast_path || (plan->mode != CROSSCLR_MODE_FP32 && plan->mode != CROSSCLR_MODE_BF16X3)) return 0;
     return 2 * plan->stash_bytes <= ((size_t)16 << 30) ? 2 * plan->stash_bytes : 0;
 }
 extern "C" size_t crossclr_stash_bytes_s(const crossclr_plan* plan) { return stash_bytes_s(plan); }
@@ -966,7 +1017,8 @@ extern "C" int crossclr_forward_save_s(const crossclr_plan* plan, const void* xh
         return forward_generic(plan, g, xhat, xhat, out, kcols, shift, 2, stream, static_cast<float*>(stash), wide_two_pass(plan) ? shift : nullptr);
     }
     if (!env_knobs().disable_symmetric)
-        return forward_generic_sym<float>(plan, g, xhat, out, kcols, part + ws_colpart_off(plan), header, stream, static_cast<float*>(stash), shift);
+        return is_x3(plan) ? forward_generic_sym<x3_t>(plan, g, xhat, out, kcols, part + ws_colpart_off(plan), header, stream, static_cast<float*>(stash), shift)
+                           : forward_generic_sym<float>(plan, g, xhat, out, kcols, part + ws_colpart_off(plan), header, stream, static_cast<float*>(stash), shift);
     rc = device_zero_header(header, stream);
     if (rc) return rc;
     return forward_generic(plan, g, xhat, xhat, out, kcols, shift, 2, stream, static_cast<float*>(stash));
@@ -1006,6 +1058,7 @@ extern "C" int crossclr_backward_saved_s(const crossclr_plan* plan, const void* 
         rc = fast_backward_saved(plan, gt, xhat, stash, zeros, zeros, rz, wrz, gbuf, 1, krows, krows, 2, stream);
         return rc ? fail(rc, "fast_backward_saved (two-pass, transposed): unsupported Dpad %d", plan->Dpad) : launch_status("fast_bwd_dsl_kernel (two-pass pair)");
     }
+    if (is_x3(plan)) return backward_saved_x3<true>(plan, g, xhat, stash, rz, wrz, krows, gbuf, accumulate, stream);
 #endif
     const int NQ = 2 * plan->bpad / 32;
     const int tps = (NQ + plan->bwd_slices - 1) / plan->bwd_slices;
@@ -1052,7 +1105,7 @@ static int backward_generic(const crossclr_plan* p, const Geo& g, const void* ro
     else CROSSCLR_LB(64);
 #undef CROSSCLR_LB
 #undef CROSSCLR_LB2
-    return launch_status("bwd_kernel");
+    return launch_status(glabel<T>("bwd_kernel", "bwd_kernel<x3_t>"));
 }
 
 extern "C" int crossclr_backward(const crossclr_plan* plan, const void* xhat_rows, const void* xhat_cols,
@@ -1086,6 +1139,8 @@ extern "C" int crossclr_backward_w(const crossclr_plan* plan, const void* xhat_r
 #endif
     if (plan->mode == CROSSCLR_MODE_FP32)
         return backward_generic<float>(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, nullptr, nullptr, stream);
+    if (is_x3(plan))
+        return backward_generic<x3_t>(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, nullptr, nullptr, stream);
     return backward_generic<bf16_t>(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, nullptr, nullptr, stream);
 }
 
@@ -1106,6 +1161,8 @@ extern "C" int crossclr_backward_s(const crossclr_plan* plan, const void* xhat_r
     if (rc) return rc;
     if (plan->mode == CROSSCLR_MODE_FP32)
         return backward_generic<float>(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, shift_rows, shift_cols, stream);
+    if (is_x3(plan))
+        return backward_generic<x3_t>(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, shift_rows, shift_cols, stream);
     return backward_generic<bf16_t>(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, shift_rows, shift_cols, stream);
 }
 
@@ -1114,6 +1171,7 @@ extern "C" int crossclr_backward_s(const crossclr_plan* plan, const void* xhat_r
 // `first_rank`, `nranks`: column ranks first_rank .. first_rank+nranks-1 (mod plan->world) of the WHOLE gathered operand.
 static int rect_geo(const crossclr_plan* plan, int first_rank, int nranks, float temperature, float negative_weight, Geo* g,
                     bool allow_row_shift = false) {
+    if (is_x3(plan)) return refuse_x3("rank-range entry points");
     if (first_rank < 0 || first_rank >= plan->world || nranks < 1 || nranks >= plan->world)
         return fail(CROSSCLR_E_ARG, "bad first_rank/nranks %d/%d for world %d", first_rank, nranks, plan->world);
     for (int i = 0; i < nranks; ++i)
@@ -1145,6 +1203,7 @@ extern "C" int crossclr_forward_rect_save(const crossclr_plan* plan, const void*
                                           const crossclr_sample_weights* sw, float* part, int slot0, float* colsum_out,
                                           void* stash, void* stream) {
     if (!plan || !xhat_rows || !xhat_all || !part || !stash || (with_colsums && !colsum_out)) return fail(CROSSCLR_E_ARG, "NULL argument");
+    if (is_x3(plan)) return refuse_x3("crossclr_forward_rect_save");
 #ifdef CROSSCLR_NO_FAST
     return fail(CROSSCLR_E_ARG, "crossclr_forward_rect_save needs the register-resident path");
 #else
@@ -1194,6 +1253,7 @@ extern "C" int crossclr_backward_rect_saved(const crossclr_plan* plan, const voi
                                             const float* wrz_rows, const float* rz_all, const float* wrz_all,
                                             const crossclr_sample_weights* sw, float* gbuf, int accumulate, void* stream) {
     if (!plan || !xhat_all || !stash || !rz_rows || !wrz_rows || !rz_all || !wrz_all || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
+    if (is_x3(plan)) return refuse_x3("crossclr_backward_rect_saved");
 #ifdef CROSSCLR_NO_FAST
     return fail(CROSSCLR_E_ARG, "crossclr_backward_rect_saved needs the register-resident path");
 #else
@@ -1503,6 +1563,7 @@ extern "C" int crossclr_backward_finish_p(const crossclr_plan* plan, const float
 static int score_geo(const crossclr_plan* p, float margin, Geo* g) {
     if (!p) return fail(CROSSCLR_E_ARG, "plan is NULL");
     if (p->world != 1) return fail(CROSSCLR_E_ARG, "score statistics are single-device (plan->world must be 1)");
+    if (is_x3(p)) return refuse_x3("score statistics / max-margin");
     if (!isfinite(margin)) return fail(CROSSCLR_E_ARG, "margin must be finite");
     memset(g, 0, sizeof(*g));
     g->b = p->b; g->bpad = p->bpad; g->D = p->D; g->Dpad = p->Dpad;

@@ -26,6 +26,10 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 typedef unsigned short bf16_t;  // storage type of a bf16 element in memory
+// storage type of one element of the split operand (compute_mode "bf16x3"): x = hi + lo, hi = bf16(x), lo = bf16(x - hi), both
+// round-to-nearest-even.  A row is laid out in 128-byte chunks of 32 elements, planar: the 32 hi values (64 B), then the 32 lo values.
+// Only its size (4 bytes per element: rows, pitches and K-chunks are those of an fp32 operand) and Operand<x3_t> give it meaning.
+struct x3_t { unsigned int raw; };
 
 constexpr int kRowPad = 128;     // rows of every packed operand are padded to this
 // host side: the launchers record which kernel template a forward (0) / gradient-product (1) launch of this thread went to
@@ -298,6 +302,7 @@ template <typename T> struct Operand;
 template <> struct Operand<float> {
     typedef float elem;
     static constexpr int kChunkElems = 32;  // 128 B
+    static constexpr int kSteps = 4;        // load / mma steps per chunk
     typedef f32x4 frag;                     // 4 consecutive k values of one row
     // one step s (0..3) of a chunk consumes 16-byte piece 2*s+half of each row and issues 4 MFMAs
     static __device__ __forceinline__ frag load(const unsigned char* tile, int row, int s, int half) {
@@ -313,12 +318,41 @@ template <> struct Operand<float> {
 template <> struct Operand<bf16_t> {
     typedef bf16_t elem;
     static constexpr int kChunkElems = 64;  // 128 B
+    static constexpr int kSteps = 4;
     typedef bf16x8 frag;                    // 8 consecutive k values of one row
     static __device__ __forceinline__ frag load(const unsigned char* tile, int row, int s, int half) {
         return *reinterpret_cast<const bf16x8*>(tile + ktile_off(row, 2 * s + half));
     }
     static __device__ __forceinline__ f32x16 mma(frag a, frag b, f32x16 c) { return mfma_32x32x16_bf16(a, b, c); }
 };
+
+// split operand: a 128-byte chunk = 32 elements, hi in 16-byte pieces 0..3, lo in pieces 4..7.  Step s (0..1) is one 16-deep k-step:
+// piece 2*s+half of each half; the product hi.hi + hi.lo + lo.hi is three bf16 MFMAs into the same accumulator (lo.lo, below 2^-16
+// relative, is left out).
+template <> struct Operand<x3_t> {
+    typedef x3_t elem;
+    static constexpr int kChunkElems = 32;  // 128 B
+    static constexpr int kSteps = 2;
+    struct frag { bf16x8 hi, lo; };          // 8 consecutive k values of one row, both parts
+    static __device__ __forceinline__ frag load(const unsigned char* tile, int row, int s, int half) {
+        frag f;
+        f.hi = *reinterpret_cast<const bf16x8*>(tile + ktile_off(row, 2 * s + half));
+        f.lo = *reinterpret_cast<const bf16x8*>(tile + ktile_off(row, 4 + 2 * s + half));
+        return f;
+    }
+    static __device__ __forceinline__ f32x16 mma(frag a, frag b, f32x16 c) {
+        c = mfma_32x32x16_bf16(a.hi, b.hi, c);
+        c = mfma_32x32x16_bf16(a.hi, b.lo, c);
+        return mfma_32x32x16_bf16(a.lo, b.hi, c);
+    }
+};
+// byte offset of element d of a split row (hi; + 64 for lo)
+__host__ __device__ __forceinline__ int x3_byte(int d) { return (d >> 5) * 128 + (d & 31) * 2; }
+// the two parts of x, round-to-nearest-even (x - hi is exact in fp32)
+__device__ __forceinline__ void x3_split(float x, bf16_t* hi, bf16_t* lo) {
+    *hi = f32_to_bf16_bits(x);
+    *lo = f32_to_bf16_bits(x - bf16_bits_to_f32(*hi));
+}
 
 // Stage R rows x 128 bytes (byte column kb of rows r0.. of a row-major array with row pitch
 // `pitch` bytes) into registers, then into a swizzled K-tile.  NT threads cooperate.

@@ -26,6 +26,14 @@ __device__ __forceinline__ void in_store(in_f16* p, size_t i, double v) {
 }
 __device__ __forceinline__ void op_store(float* p, size_t i, float v) { p[i] = v; }
 __device__ __forceinline__ void op_store(bf16_t* p, size_t i, float v) { p[i] = f32_to_bf16_bits(v); }
+// split operand (x3_t): element i of a row at its place in the row's 128-byte chunks, hi and lo (i is the column: rows start at chunks)
+__device__ __forceinline__ void op_store(x3_t* p, size_t i, float v) {
+    bf16_t h, l;
+    x3_split(v, &h, &l);
+    unsigned char* c = reinterpret_cast<unsigned char*>(p) + (i >> 5) * 128 + (i & 31) * 2;
+    *reinterpret_cast<bf16_t*>(c) = h;
+    *reinterpret_cast<bf16_t*>(c + 64) = l;
+}
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
@@ -85,6 +93,17 @@ __device__ __forceinline__ void op_store4(bf16_t* row, int d, const float (&v)[4
     o[0] = (uint32_t)f32_to_bf16_bits(v[0]) | ((uint32_t)f32_to_bf16_bits(v[1]) << 16);
     o[1] = (uint32_t)f32_to_bf16_bits(v[2]) | ((uint32_t)f32_to_bf16_bits(v[3]) << 16);
     *reinterpret_cast<u32x2*>(row + d) = o;
+}
+__device__ __forceinline__ void op_store4(x3_t* row, int d, const float (&v)[4]) {
+    bf16_t h[4], l[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x3_split(v[j], &h[j], &l[j]);
+    u32x2 oh, ol;
+    oh[0] = (uint32_t)h[0] | ((uint32_t)h[1] << 16); oh[1] = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
+    ol[0] = (uint32_t)l[0] | ((uint32_t)l[1] << 16); ol[1] = (uint32_t)l[2] | ((uint32_t)l[3] << 16);
+    unsigned char* c = reinterpret_cast<unsigned char*>(row) + x3_byte(d);
+    *reinterpret_cast<u32x2*>(c) = oh;
+    *reinterpret_cast<u32x2*>(c + 64) = ol;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -385,7 +404,7 @@ __global__ void __launch_bounds__(256, 2) fwd_sums_kernel(const T* rows, const T
                 fq.fetch(cbase, pitch, (kc + 2) * 128, tid);
             }
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
+            for (int s = 0; s < Op::kSteps; ++s) {
                 typename Op::frag a[2], bfr[2];
 #pragma unroll
                 for (int x = 0; x < 2; ++x) {
@@ -801,6 +820,21 @@ template <> __device__ __forceinline__ int xq_off<bf16_t, 64>(int q, int d) { re
 template <> __device__ __forceinline__ int xq_off<bf16_t, 128>(int q, int d) { return xq_off_bf16<128>(q, d); }
 template <> __device__ __forceinline__ int xq_off<bf16_t, 256>(int q, int d) { return xq_off_bf16<256>(q, d); }
 template <> __device__ __forceinline__ int xq_off<bf16_t, 512>(int q, int d) { return xq_off_bf16<512>(q, d); }
+// split operand: the slice holds the rows' raw 128-byte chunks (e = byte / 4 inside the slice row); 16-byte piece c of row q sits at piece
+// c ^ ((q & 3) << 2), so the four rows a transpose-read group touches (q & 3 = 0..3) cover four different 64-byte bank groups.  A slice row
+// has DC / 4 >= 16 pieces: the XOR stays inside the row.
+template <int DC> __device__ __forceinline__ int xq_off_x3(int q, int e) {
+    return q * DC * 4 + (((e >> 2) ^ ((q & 3) << 2)) << 4) + (e & 3) * 4;
+}
+template <> __device__ __forceinline__ int xq_off<x3_t, 64>(int q, int d) { return xq_off_x3<64>(q, d); }
+template <> __device__ __forceinline__ int xq_off<x3_t, 128>(int q, int d) { return xq_off_x3<128>(q, d); }
+template <> __device__ __forceinline__ int xq_off<x3_t, 256>(int q, int d) { return xq_off_x3<256>(q, d); }
+template <> __device__ __forceinline__ int xq_off<x3_t, 512>(int q, int d) { return xq_off_x3<512>(q, d); }
+// LDS byte of element (q, d) of the slice, part `lo` (0: hi, 1: lo): 8-byte aligned for d % 4 == 0
+template <int DC> __device__ __forceinline__ int xq_elem_x3(int q, int d, int lo) {
+    const int piece = 8 * (d >> 5) + 4 * lo + ((d & 31) >> 3);
+    return q * DC * 4 + ((piece ^ ((q & 3) << 2)) << 4) + (d & 7) * 2;
+}
 
 // phase B store of 4 consecutive-q weights of row p (q0 multiple of 4)
 __device__ __forceinline__ void w_store4(unsigned char* wt, int p, int q0, f32x4 w, float*) {
@@ -813,6 +847,19 @@ __device__ __forceinline__ void w_store4(unsigned char* wt, int p, int q0, f32x4
     pk[0] = (uint32_t)f32_to_bf16_bits(w[0]) | ((uint32_t)f32_to_bf16_bits(w[1]) << 16);
     pk[1] = (uint32_t)f32_to_bf16_bits(w[2]) | ((uint32_t)f32_to_bf16_bits(w[3]) << 16);
     *reinterpret_cast<u32x2*>(wt + ktile_off(p, q0 >> 3) + (q0 & 4) * 2) = pk;
+}
+
+// split operand: W_hi and W_lo as two bf16 K-tiles [64][64], lo 8 KiB behind hi
+__device__ __forceinline__ void w_store4(unsigned char* wt, int p, int q0, f32x4 w, x3_t*) {
+    bf16_t h[4], l[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x3_split(w[j], &h[j], &l[j]);
+    u32x2 ph, pl;
+    ph[0] = (uint32_t)h[0] | ((uint32_t)h[1] << 16); ph[1] = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
+    pl[0] = (uint32_t)l[0] | ((uint32_t)l[1] << 16); pl[1] = (uint32_t)l[2] | ((uint32_t)l[3] << 16);
+    const int o = ktile_off(p, q0 >> 3) + (q0 & 4) * 2;
+    *reinterpret_cast<u32x2*>(wt + o) = ph;
+    *reinterpret_cast<u32x2*>(wt + 64 * 128 + o) = pl;
 }
 
 // phase C inner products for one wave: rows 32*wr.., DC/2 embedding columns starting at dw0
@@ -853,6 +900,32 @@ __device__ __forceinline__ void bwd_gemm2(const unsigned char* wt, const unsigne
             struct { s16x4 lo, hi; } pair = {lo, hi};  // k-slots 0..3 <- rows q0.., 4..7 <- rows q0+4..
             const bf16x8 bfr = __builtin_bit_cast(bf16x8, pair);
             acc[dt] = mfma_32x32x16_bf16(a, bfr, acc[dt]);
+        }
+    }
+}
+
+// split operand: the bf16 form with hi and lo on both sides, W_hi.X_hi + W_hi.X_lo + W_lo.X_hi per 16 columns q
+template <int DC>
+__device__ __forceinline__ void bwd_gemm2(const unsigned char* wt, const unsigned char* xq, int wr, int dw0,
+                                          int lane, f32x16 (&acc)[DC / 64], x3_t*) {
+    const int half = lane >> 5, l31 = lane & 31;
+    const int grp = lane >> 4, i16 = lane & 15, jrow = i16 >> 2, piece = i16 & 3;
+    const int dsub = grp & 1;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+        const int ao = ktile_off(32 * wr + l31, 2 * ks + half);
+        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(wt + ao);
+        const bf16x8 al = *reinterpret_cast<const bf16x8*>(wt + 64 * 128 + ao);
+#pragma unroll
+        for (int dt = 0; dt < DC / 64; ++dt) {
+            const int dcol = dw0 + 32 * dt + 16 * dsub + 4 * piece;
+            const int q0 = 16 * ks + 8 * half + jrow;
+            struct { s16x4 a, b; } ph = {lds_read_tr16_b64(xq + xq_elem_x3<DC>(q0, dcol, 0)), lds_read_tr16_b64(xq + xq_elem_x3<DC>(q0 + 4, dcol, 0))};
+            struct { s16x4 a, b; } pl = {lds_read_tr16_b64(xq + xq_elem_x3<DC>(q0, dcol, 1)), lds_read_tr16_b64(xq + xq_elem_x3<DC>(q0 + 4, dcol, 1))};
+            const bf16x8 bh = __builtin_bit_cast(bf16x8, ph), bl = __builtin_bit_cast(bf16x8, pl);
+            acc[dt] = mfma_32x32x16_bf16(ah, bh, acc[dt]);
+            acc[dt] = mfma_32x32x16_bf16(ah, bl, acc[dt]);
+            acc[dt] = mfma_32x32x16_bf16(al, bh, acc[dt]);
         }
     }
 }
@@ -944,7 +1017,7 @@ __global__ void __launch_bounds__(256) bwd_kernel(const T* rows, const T* cols, 
                 sq.fetch(cbase, pitch, (kc + 1) * 128, tid);
             }
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
+            for (int s = 0; s < Op::kSteps; ++s) {
                 typename Op::frag a = Op::load(tileQ, 32 * wq + l31, s, half);
                 typename Op::frag bfr = Op::load(tileP, 32 * wp + l31, s, half);
                 acc = Op::mma(a, bfr, acc);

@@ -15,11 +15,15 @@ criterion is twice differentiable: under `create_graph=True` the HIP backward is
 own backward is crossclr_second_order (Hessian-vector product in closed form on the device, exact fp32).
 
 Keyword-only additions (defaults reproduce the reference's single-process behaviour):
-  compute_mode   "auto" | "fp32" | "bf16".  fp32 = exact-fp32 MFMA; bf16 = bf16 operands with
+  compute_mode   "auto" | "fp32" | "bf16" | "bf16x3".  fp32 = exact-fp32 MFMA; bf16 = bf16 operands with
                  fp32 accumulation (the BASELINE headline mode).  auto = bf16 when the global
                  batch is >= 1024 rows (where its error is ~1e-5 on the loss; a one-time warning says so
                  for fp32/fp64 inputs), fp32 below that and whenever max(1,|w|)/temperature > 128
                  (small temperatures: the two-pass soft-max regime, where bf16 cosines are too coarse).
+                 bf16x3 (opt-in, single device only) = fp32-accurate products on the bf16 matrix cores: every
+                 unit row is split into hi = bf16(x) and lo = bf16(x - hi), every product is hi.hi + hi.lo + lo.hi
+                 (three bf16 MFMAs into one fp32 accumulator); the fp32 mode's accuracy bars at a fraction of its
+                 matrix cost.  `auto` never picks it; with a multi-rank process_group it raises ValueError.
   process_group  a torch.distributed group: the batch is the concatenation of every rank's rows
                  (equal count per rank); the returned loss is the GLOBAL loss on every rank and the
                  gradients are exactly d(global loss)/d(local rows).
@@ -79,6 +83,8 @@ def _resolve_mode(compute_mode: str, global_batch: int, in_dtype=None, small_tem
         return nat.MODE_FP32
     if compute_mode == "bf16":
         return nat.MODE_BF16
+    if compute_mode == "bf16x3":
+        return nat.MODE_BF16X3
     if compute_mode == "auto":
         # bf16 rounds a cosine to 2^-9; the logit carries that times 1/tau: at small temperatures (the two-pass regime) only
         # exact-fp32 products keep the 1e-3 loss bar, and the generic kernels run there in either mode anyway
@@ -92,7 +98,7 @@ def _resolve_mode(compute_mode: str, global_batch: int, in_dtype=None, small_tem
                           "reference); pass compute_mode='fp32' for exact-fp32 products. This message is shown once."
                           % (AUTO_BF16_MIN_GLOBAL_BATCH, str(in_dtype).replace("torch.", "")), stacklevel=3)
         return nat.MODE_BF16
-    raise ValueError(f"compute_mode must be 'auto', 'fp32' or 'bf16', got {compute_mode!r}")
+    raise ValueError(f"compute_mode must be 'auto', 'fp32', 'bf16' or 'bf16x3', got {compute_mode!r}")
 
 
 class _Workspace:
@@ -729,6 +735,9 @@ def _forward_impl(video: torch.Tensor, text: torch.Tensor, temperature: float, n
     sharded = world > 1 or (group is not None and os.environ.get("CROSSCLR_FORCE_SHARDED_PATH") == "1")
     small_tau = bool(lib.crossclr_needs_row_shift(float(temperature), float(negative_w)))
     mode = _resolve_mode(compute_mode, b * world, video.dtype, small_tau)
+    if mode == nat.MODE_BF16X3 and sharded:
+        raise ValueError("bf16x3 is single-device: compute_mode='bf16x3' takes no process_group of more than one rank "
+                         "(nor CROSSCLR_FORCE_SHARDED_PATH=1)")
     plan = _plan_for(b, D, world, rank, mode)
     if not sharded and project is None:
         return _forward_step(video, text, temperature, negative_w, plan, mode, negative_scale, loss_weight, save_for_backward, prenormalized)

@@ -20,7 +20,8 @@
  *
  * Data layout ("packed operand"): one rank's normalised embeddings are a dense row-major array
  *   X[2][bpad][Dpad]   (modality 0 = video rows, 1 = text rows), zero padded,
- * element type fp32 (CROSSCLR_MODE_FP32) or bf16 (CROSSCLR_MODE_BF16).  A column operand made of
+ * element type fp32 (CROSSCLR_MODE_FP32) or bf16 (CROSSCLR_MODE_BF16); CROSSCLR_MODE_BF16X3 plans hold 4 bytes per element, every
+ * 32 elements of a row one 128-byte chunk: the 32 bf16 values hi = bf16(x), then the 32 bf16 values lo = bf16(x - hi).  A column operand made of
  * `col_ranks` such arrays back to back (what an RCCL all-gather of packed operands produces) is
  *   Xcols[col_ranks][2][bpad][Dpad].
  * Per-row statistics use the same [2][bpad] (rows) / [col_ranks][2][bpad] (columns) indexing.
@@ -35,7 +36,7 @@ extern "C" {
 #endif
 
 #define CROSSCLR_LAUNCH_GROUPS 8   /* launch groups the forward workspace has room for */
-#define CROSSCLR_ABI_VERSION 7
+#define CROSSCLR_ABI_VERSION 8
 
 /* input element types (crossclr_normalize / crossclr_backward_finish) */
 #define CROSSCLR_IN_F32 0
@@ -46,6 +47,12 @@ extern "C" {
 /* compute modes */
 #define CROSSCLR_MODE_FP32 0 /* v_mfma_f32_32x32x2_f32: exact fp32 products            */
 #define CROSSCLR_MODE_BF16 1 /* v_mfma_f32_32x32x16_bf16: bf16 operands, fp32 accumulate */
+/* ABI 8: fp32-accurate products on the bf16 matrix cores.  Every unit row is split into hi = bf16(x), lo = bf16(x - hi) and every product
+ * is hi.hi + hi.lo + lo.hi, three v_mfma_f32_32x32x16_bf16 into one fp32 accumulator (relative product error ~2^-16 of the lo.lo term
+ * left out, vs 2^-8 for bf16).  Single-device plans only (world == 1): the generic tiled kernels of the fp32 mode with the split operand,
+ * the fp32 stash of the fp32 mode (the same bytes, the same CROSSCLR_MAX_STASH_GB rule), the same step layouts.  Score statistics,
+ * max-margin, projection, second-order and the rectangular / pair entry points of sharded runs refuse a BF16X3 plan (CROSSCLR_E_ARG). */
+#define CROSSCLR_MODE_BF16X3 2 /* 3 x v_mfma_f32_32x32x16_bf16 on hi/lo bf16 parts, fp32 accumulate */
 
 /* error codes */
 #define CROSSCLR_OK 0

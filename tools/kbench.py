@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel timing at one shape (default: BASELINE config 3).  usage: kbench.py [B] [D] [mode]"""
+"""Per-kernel timing at one shape (default: BASELINE config 3).  usage: kbench.py [B] [D] [mode: bf16 | bf16x3 | fp32]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, crossclr_amd
@@ -11,7 +11,7 @@ mode = sys.argv[3] if len(sys.argv) > 3 else "bf16"
 v, t = orc.make_inputs("randn", B, D, 1234)
 v, t = v.cuda(), t.cuda()
 st = _profile.stage_times(v, t, 0.03, 0.8, mode, iters=20, warmup=3, settle=int(os.environ.get("KBENCH_SETTLE", "30")))
-peak = 2500.0 if mode == "bf16" else 157.3
+peak = {"bf16": 2500.0, "bf16x3": 2500.0 / 3}.get(mode, 157.3)     # bf16x3: three bf16 MFMAs per product
 f = 6.0 * B * B * D / (st["step_forward"] * 1e-3) / 1e12
 b = 8.0 * B * B * D / (st["step_backward"] * 1e-3) / 1e12
 tot = sum(st[k] for k in ("normalize", "step_forward", "forward_finish", "step_backward", "backward_finish"))
