@@ -5,6 +5,7 @@
 #include "../../include/crossclr.h"
 #include "crossclr_kernels_generic.h"
 #include "crossclr_kernels_hvp.h"
+#include "crossclr_kernels_topk.h"
 #ifndef CROSSCLR_NO_FAST
 #include "crossclr_kernels_fast.h"
 #include "crossclr_kernels_project.h"
@@ -1689,6 +1690,108 @@ extern "C" int crossclr_maxmargin_backward_finish(const crossclr_plan* plan, con
     crossclr_sample_weights sw = {nullptr, nullptr, active};
     return crossclr_backward_finish_p(plan, gbuf, im, s, ld_im, ld_s, in_dtype, ones, 0.5f * (float)plan->b, &sw, grad_out, grad_im, grad_s,
                                       ld_gim, ld_gs, 1, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// retrieval: fused similarity + top-k over two independent sets (crossclr_kernels_topk.h)
+static int topk_mode_ok(int mode) { return mode == CROSSCLR_MODE_FP32 || mode == CROSSCLR_MODE_BF16 || mode == CROSSCLR_MODE_BF16X3; }
+static int topk_set_ok(const char* what, int rows, int D) {
+    if (rows < 1 || D < 1) return fail(CROSSCLR_E_ARG, "%s: empty set (rows=%d D=%d)", what, rows, D);
+    if (rows > (1 << 30) || D > (1 << 20)) return fail(CROSSCLR_E_ARG, "%s: set too large (rows=%d D=%d)", what, rows, D);
+    return CROSSCLR_OK;
+}
+static int topk_args_ok(const char* what, int nq, int ng, int D, int k) {
+    if (int rc = topk_set_ok(what, nq, D)) return rc;
+    if (int rc = topk_set_ok(what, ng, D)) return rc;
+    if (k < 1) return fail(CROSSCLR_E_ARG, "%s: k must be at least 1 (got %d)", what, k);
+    if (k > kTopkMaxK) return fail(CROSSCLR_E_ARG, "%s: k = %d is above the limit of %d (crossclr_topk_max_k)", what, k, kTopkMaxK);
+    if (k > ng) return fail(CROSSCLR_E_ARG, "%s: k = %d is larger than the gallery (%d rows)", what, k, ng);
+    return CROSSCLR_OK;
+}
+// column splits: enough thread blocks for two per CU of an MI355X (as the generic forward's grid), at most one per column tile, at most
+// kTopkMaxCandidates / k (the merge kernel's list); `requested` > 0 replaces the first rule.  Every split owns at least one tile.
+static int topk_splits(int nq, int ng, int k, int requested) {
+    const int row_blocks = round_up(nq, kRowPad) / 128, ntiles = round_up(ng, kRowPad) / 128;
+    int ns = requested > 0 ? requested : (512 + row_blocks - 1) / row_blocks;
+    if (ns > kTopkMaxCandidates / k) ns = kTopkMaxCandidates / k;
+    if (ns > ntiles) ns = ntiles;
+    if (ns < 1) ns = 1;
+    const int tps = (ntiles + ns - 1) / ns;
+    return (ntiles + tps - 1) / tps;
+}
+extern "C" int crossclr_topk_max_k(void) { return kTopkMaxK; }
+extern "C" size_t crossclr_topk_operand_bytes(int rows, int D, int mode) {
+    if (rows < 1 || D < 1 || rows > (1 << 30) || D > (1 << 20) || !topk_mode_ok(mode)) return 0;
+    return (size_t)round_up(rows, kRowPad) * (size_t)round_up(D, 64) * (mode == CROSSCLR_MODE_BF16 ? 2 : 4);
+}
+template <typename TIN>
+static int topk_pack_t(const void* x, long ld, int rows, int D, int mode, int normalize, void* packed, void* stream) {
+    const int rows_pad = round_up(rows, kRowPad), Dpad = round_up(D, 64);
+    dim3 grid(rows_pad / 4), block(256);
+#define CROSSCLR_LTP(TT) do { \
+        if (normalize) LAUNCH((topk_pack_kernel<TIN, TT, true>), grid, block, stream, (const TIN*)x, ld, rows, rows_pad, D, Dpad, (TT*)packed); \
+        else LAUNCH((topk_pack_kernel<TIN, TT, false>), grid, block, stream, (const TIN*)x, ld, rows, rows_pad, D, Dpad, (TT*)packed); } while (0)
+    if (mode == CROSSCLR_MODE_FP32) CROSSCLR_LTP(float);
+    else if (mode == CROSSCLR_MODE_BF16X3) CROSSCLR_LTP(x3_t);
+    else CROSSCLR_LTP(bf16_t);
+#undef CROSSCLR_LTP
+    return launch_status("topk_pack_kernel");
+}
+extern "C" int crossclr_topk_pack(const void* x, long ld, int rows, int D, int in_dtype, int mode, int normalize, void* packed, void* stream) {
+    if (!x || !packed) return fail(CROSSCLR_E_ARG, "NULL argument");
+    if (int rc = topk_set_ok("crossclr_topk_pack", rows, D)) return rc;
+    if (!topk_mode_ok(mode)) return fail(CROSSCLR_E_ARG, "bad mode %d", mode);
+    if (ld < D) return fail(CROSSCLR_E_ARG, "row stride smaller than D");
+    switch (in_dtype) {
+        case CROSSCLR_IN_F32: return topk_pack_t<float>(x, ld, rows, D, mode, normalize, packed, stream);
+        case CROSSCLR_IN_F64: return topk_pack_t<double>(x, ld, rows, D, mode, normalize, packed, stream);
+        case CROSSCLR_IN_F16: return topk_pack_t<in_f16>(x, ld, rows, D, mode, normalize, packed, stream);
+        case CROSSCLR_IN_BF16: return topk_pack_t<in_bf16>(x, ld, rows, D, mode, normalize, packed, stream);
+    }
+    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
+}
+extern "C" int crossclr_topk_splits(int nq, int ng, int k, int requested) {
+    if (int rc = topk_args_ok("crossclr_topk_splits", nq, ng, 1, k)) return rc;
+    return topk_splits(nq, ng, k, requested);
+}
+extern "C" size_t crossclr_topk_workspace_bytes(int nq, int ng, int k, int splits) {
+    if (nq < 1 || ng < 1 || nq > (1 << 30) || ng > (1 << 30) || k < 1 || k > kTopkMaxK || k > ng) return 0;
+    return (size_t)topk_splits(nq, ng, k, splits) * (size_t)round_up(nq, kRowPad) * (size_t)k * 8;
+}
+template <typename T>
+static void topk_select_launch(const void* q, const void* g, int nq, int ng, int Dpad, int k, int ns, float* ws_s, int* ws_i, void* stream) {
+    const int nq_pad = round_up(nq, kRowPad), ntiles = round_up(ng, kRowPad) / 128;
+    const int tps = (ntiles + ns - 1) / ns;
+    dim3 grid(nq_pad / 128, ns), block(256);
+    if (k <= 16) LAUNCH((topk_select_kernel<T, 16>), grid, block, stream, (const T*)q, (const T*)g, nq, ng, nq_pad, Dpad, k, tps, ws_s, ws_i);
+    else LAUNCH((topk_select_kernel<T, 64>), grid, block, stream, (const T*)q, (const T*)g, nq, ng, nq_pad, Dpad, k, tps, ws_s, ws_i);
+}
+extern "C" int crossclr_topk_select(const void* queries_packed, const void* gallery_packed, int nq, int ng, int D, int mode, int k, int splits,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    if (!queries_packed || !gallery_packed || !workspace) return fail(CROSSCLR_E_ARG, "NULL argument");
+    if (int rc = topk_args_ok("crossclr_topk_select", nq, ng, D, k)) return rc;
+    if (!topk_mode_ok(mode)) return fail(CROSSCLR_E_ARG, "bad mode %d", mode);
+    const int ns = topk_splits(nq, ng, k, splits);
+    const size_t entries = (size_t)ns * (size_t)round_up(nq, kRowPad) * (size_t)k;
+    if (workspace_bytes < entries * 8)
+        return fail(CROSSCLR_E_WORKSPACE, "crossclr_topk_select: workspace of %zu bytes, %zu needed (crossclr_topk_workspace_bytes)", workspace_bytes, entries * 8);
+    float* ws_s = static_cast<float*>(workspace);
+    int* ws_i = reinterpret_cast<int*>(ws_s + entries);
+    const int Dpad = round_up(D, 64);
+    if (mode == CROSSCLR_MODE_FP32) topk_select_launch<float>(queries_packed, gallery_packed, nq, ng, Dpad, k, ns, ws_s, ws_i, stream);
+    else if (mode == CROSSCLR_MODE_BF16X3) topk_select_launch<x3_t>(queries_packed, gallery_packed, nq, ng, Dpad, k, ns, ws_s, ws_i, stream);
+    else topk_select_launch<bf16_t>(queries_packed, gallery_packed, nq, ng, Dpad, k, ns, ws_s, ws_i, stream);
+    return launch_status("topk_select_kernel");
+}
+extern "C" int crossclr_topk_merge(const void* workspace, int nq, int ng, int k, int splits, float* scores, int* indices, void* stream) {
+    if (!workspace || !scores || !indices) return fail(CROSSCLR_E_ARG, "NULL argument");
+    if (int rc = topk_args_ok("crossclr_topk_merge", nq, ng, 1, k)) return rc;
+    const int ns = topk_splits(nq, ng, k, splits), nq_pad = round_up(nq, kRowPad);
+    const float* ws_s = static_cast<const float*>(workspace);
+    const int* ws_i = reinterpret_cast<const int*>(ws_s + (size_t)ns * nq_pad * k);
+    const int lpr = ns * k > 128 ? 256 : 64, rpb = 256 / lpr;      // long candidate lists: a whole block per row
+    LAUNCH(topk_merge_kernel, dim3((nq + rpb - 1) / rpb), dim3(256), stream, ws_s, ws_i, nq, nq_pad, ns, k, lpr, scores, indices);
+    return launch_status("topk_merge_kernel");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -13,13 +13,15 @@ generic tiled backward with indicator weights (`crossclr_maxmargin_backward[_fin
 
 `retrieval_ranks` is the evaluation step that follows training in the CrossCLR / COOT pipelines (not in the reference
 repository): rank of each sample's partner among all candidates of the other modality, both directions, from the same kernels
-with margin 0 (count of candidates scoring strictly higher than the partner).
+with margin 0 (count of candidates scoring strictly higher than the partner).  `retrieval_topk` is its other half: WHO was retrieved --
+the k best candidates of every query over two independent sets of any sizes, from the same tiled product with a selection epilogue
+(`crossclr_topk_select`, `crossclr_topk_merge`).
 """
 from __future__ import annotations
 
 import ctypes
 import os
-from typing import Dict
+from typing import Dict, Tuple
 
 import torch
 from torch import nn
@@ -159,3 +161,73 @@ def retrieval_ranks(video_features: torch.Tensor, text_features: torch.Tensor, *
         out[key] = torch.stack([(r < 1).double().mean(), (r < 5).double().mean(), (r < 10).double().mean(),
                                 r.median() + 1.0, r.mean() + 1.0])
     return out
+
+
+def _topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, normalize: bool, compute_mode: str, splits: int = 0):
+    """`retrieval_topk` with the number of column splits exposed (0 = the library's choice): the result does not depend on it."""
+    for name, t in (("queries", queries), ("gallery", gallery)):
+        if t.dim() != 2:
+            raise RuntimeError(f"retrieval_topk expects 2-D [rows, embed_dim] inputs, got {name} of shape {tuple(t.shape)}")
+    if queries.shape[1] != gallery.shape[1]:
+        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({queries.shape[0]}x{queries.shape[1]} and "
+                           f"{gallery.shape[1]}x{gallery.shape[0]})")
+    if queries.dtype != gallery.dtype:
+        raise RuntimeError(f"expected both inputs to have the same dtype, got {queries.dtype} and {gallery.dtype}")
+    if queries.dtype not in _IN_DTYPE:
+        raise RuntimeError(f"unsupported input dtype {queries.dtype}")
+    if queries.device != gallery.device:
+        raise RuntimeError("queries and gallery must be on the same device")
+    if not queries.is_cuda and nat.backend() != "emu-host":
+        raise RuntimeError("the HIP path needs inputs on the GPU (got a CPU tensor); there is no CPU fallback")
+    nq, D = queries.shape
+    ng = gallery.shape[0]
+    if nq == 0 or ng == 0 or D == 0:
+        raise RuntimeError("empty set")
+    lib = nat.library()
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k must be at least 1, got {k}")
+    if k > ng:
+        raise ValueError(f"k = {k} is larger than the gallery ({ng} rows)")
+    if k > lib.crossclr_topk_max_k():
+        raise ValueError(f"k = {k} is above the library's limit of {lib.crossclr_topk_max_k()}")
+    mode = _resolve_mode(compute_mode, max(nq, ng), queries.dtype)
+    q, g = _row_major(queries.detach()), _row_major(gallery.detach())
+    dev, in_dtype = q.device, _IN_DTYPE[q.dtype]
+    with _device_of(q):
+        stream = _stream_for(q)
+        qp = torch.empty(lib.crossclr_topk_operand_bytes(nq, D, mode), dtype=torch.uint8, device=dev)
+        gp = torch.empty(lib.crossclr_topk_operand_bytes(ng, D, mode), dtype=torch.uint8, device=dev)
+        nat.check(lib.crossclr_topk_pack(_ptr(q), q.stride(0), nq, D, in_dtype, mode, int(normalize), _ptr(qp), stream))
+        nat.check(lib.crossclr_topk_pack(_ptr(g), g.stride(0), ng, D, in_dtype, mode, int(normalize), _ptr(gp), stream))
+        ws = torch.empty(lib.crossclr_topk_workspace_bytes(nq, ng, k, splits), dtype=torch.uint8, device=dev)
+        scores = torch.empty(nq, k, dtype=torch.float32, device=dev)
+        index = torch.empty(nq, k, dtype=torch.int32, device=dev)
+        nat.check(lib.crossclr_topk_select(_ptr(qp), _ptr(gp), nq, ng, D, mode, k, splits, _ptr(ws), ws.numel(), stream))
+        nat.check(lib.crossclr_topk_merge(_ptr(ws), nq, ng, k, splits, _ptr(scores), _ptr(index), stream))
+        return scores, index.to(torch.int64)
+
+
+def retrieval_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, *, normalize: bool = True,
+                   compute_mode: str = "fp32") -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k best gallery rows of every query: `scores` [Nq, k] float32 and `indices` [Nq, k] int64 of the k largest
+    S[i, j] = q_i . g_j (cosines with normalize=True: rows L2-normalised like the loss does; normalize=False: rows as given).
+
+    `queries` [Nq, D] and `gallery` [Ng, D] are independent sets (several captions per clip, a few queries against a large gallery); the
+    Nq x Ng score matrix is never materialised.  Row i is sorted: higher score first, among bit-equal scores the lower gallery index first
+    (identical gallery rows score bit-equal); the result does not depend on how the launch is cut.  No autograd (inputs are detached);
+    device tensors come back and nothing synchronises the host.  compute_mode: "fp32" (default, exact-fp32 products), "bf16", "bf16x3",
+    or "auto" (decided on max(Nq, Ng)).  ValueError for k < 1, k > Ng or k above the library's limit (64); RuntimeError for mismatched D or
+    an empty set.
+
+    R@k against arbitrary ground truth (`target[i]` = the gallery row that is right for query i):
+
+        scores, indices = retrieval_topk(text_emb, video_emb, 10)
+        hit = (indices == target[:, None]).any(1)          # R@10 = hit.float().mean()
+
+    Hard negatives for the next epoch, a set against itself (column 0 is the row itself):
+
+        _, indices = retrieval_topk(emb, emb, 1 + n_neg)
+        hard_negatives = indices[:, 1:]
+    """
+    return _topk(queries, gallery, k, normalize, compute_mode)

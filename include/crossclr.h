@@ -468,6 +468,39 @@ int crossclr_maxmargin_backward_finish(const crossclr_plan* plan, const float* g
                                        long ld_s, int in_dtype, const float* ones, const float* active, const double* grad_out,
                                        void* grad_im, void* grad_s, long ld_gim, long ld_gs, void* stream);
 
+/* ---- retrieval: similarity + top-k over two INDEPENDENT sets (single device; no plan) ------------------------------------
+ * The evaluation step after training, for sets that are neither paired nor equally large (several captions per clip, a few queries
+ * against a large gallery): per query row i the k largest S[i][j] = q_i . g_j over the gallery rows j, with their indices.  The nq x ng
+ * matrix S is never materialised: the tiled similarity kernel keeps k candidates per query row and column split, a merge kernel orders them.
+ * ABI: these are NEW SYMBOLS ONLY -- no existing signature, struct or constant changed -- so CROSSCLR_ABI_VERSION stays 8 (additive-symbols
+ * policy: a binding of version 8 that does not know them keeps working; one that needs them finds them missing at load time).
+ *
+ * Operand layout (one set; the plan's X[2][bpad][Dpad] pairs two sets of equal size and does not fit): X[rows_pad][Dpad], row-major,
+ *   rows_pad = rows rounded up to 128, Dpad = D rounded up to 64, zero padded, element type by `mode` (CROSSCLR_MODE_FP32: float,
+ *   _BF16: bf16, _BF16X3: the split operand, 4 bytes per element): crossclr_topk_operand_bytes.  crossclr_topk_pack fills it from a
+ *   row-major [rows][D] array of any input dtype with row stride `ld`: normalize = 1 divides every row by max(||row||, 1e-12) exactly as
+ *   crossclr_normalize does for a modality (loss.py:79-80), normalize = 0 only casts and lays out (crossclr_pack's arithmetic).  It is a
+ *   kernel of its own, not a reuse of crossclr_normalize / crossclr_pack, which need a plan and a partner set of the same size.
+ * crossclr_topk_select   queries_packed / gallery_packed as above, both in `mode` and of width D; 1 <= k <= min(ng, crossclr_topk_max_k).
+ *   Writes, per column split, every query row's k best candidates into `workspace` (crossclr_topk_workspace_bytes; contents irrelevant before).
+ * crossclr_topk_merge    scores[nq][k] (float) and indices[nq][k] (int, gallery row numbers), row i holding its k best in this TOTAL ORDER:
+ *   higher score first, among bit-equal scores the lower index first.  Identical gallery rows give bit-equal scores (same MFMA sequence),
+ *   so they appear lower index first.  The result does not depend on the number of splits, the grid or the order blocks run in: there are
+ *   no atomics, and the k best under a strict order are one set however the columns are cut.
+ * `splits`: 0 = the library's choice (enough thread blocks for the device); > 0 = a request, cut down to what the shape allows.  Hand the
+ *   SAME value to crossclr_topk_workspace_bytes, _select and _merge; crossclr_topk_splits returns the count they all derive from it.
+ * crossclr_topk_max_k: the limit on k (64).  Size queries return 0 and the others CROSSCLR_E_ARG for k < 1, k > ng, k above the limit,
+ * an empty set or a bad mode; CROSSCLR_E_WORKSPACE for a workspace that is too small.  Nothing is allocated, nothing synchronises,
+ * everything is enqueued on `stream`.  NaN scores are not ordered (the caller's rows must be finite).                               */
+int crossclr_topk_max_k(void);
+size_t crossclr_topk_operand_bytes(int rows, int D, int mode);
+int crossclr_topk_pack(const void* x, long ld, int rows, int D, int in_dtype, int mode, int normalize, void* packed, void* stream);
+int crossclr_topk_splits(int nq, int ng, int k, int splits);
+size_t crossclr_topk_workspace_bytes(int nq, int ng, int k, int splits);
+int crossclr_topk_select(const void* queries_packed, const void* gallery_packed, int nq, int ng, int D, int mode, int k, int splits,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int crossclr_topk_merge(const void* workspace, int nq, int ng, int k, int splits, float* scores, int* indices, void* stream);
+
 /* ---- THE WHOLE STEP BEHIND TWO CALLS (ABI 6; layout handed from call to call and split workspace: ABI 7.  Single device: plan->world == 1)
  * What the reference's one class is to its caller (trainer/loss.py:68-114 `forward`, and autograd's backward through it): a binding needs
  * nothing but crossclr_make_plan, crossclr_step_plan, crossclr_step_forward and crossclr_step_backward.  The library chooses the kernels:
