@@ -703,105 +703,122 @@ extern "C" int crossclr_forward_save(const crossclr_plan* plan, const void* xhat
 }
 
 #ifndef CROSSCLR_NO_FAST
-// BF16X3 plans: the saved backward on the split operand (crossclr_kernels_saved32.h), single pass (RM = false) or two-pass (RM = true)
+// bwd_saved32_kernel / bwd_saved_x3_kernel (crossclr_kernels_saved32.h): DC columns of D per thread block -- f(std::integral_constant<int, DC>()) --
+// and `ntiles` 32-column tiles cut into plan->bwd_slices slices WITHOUT the even rounding of fast_backward_saved
+template <class F> static void saved32_with_dc(int Dpad, F f) {
+    if (Dpad % 256 == 0) f(std::integral_constant<int, 256>());
+    else if (Dpad % 128 == 0) f(std::integral_constant<int, 128>());
+    else f(std::integral_constant<int, 64>());
+}
+static dim3 saved32_grid(const crossclr_plan* plan, int DC) { return dim3(2 * plan->bpad / 64, plan->Dpad / DC, (unsigned)plan->bwd_slices); }
+static int saved32_tps(const crossclr_plan* plan, int ntiles) { return (ntiles + plan->bwd_slices - 1) / plan->bwd_slices; }
+
+// BF16X3 plans: the saved backward on the split operand, single pass (RM = false) or two-pass (RM = true)
 template <bool RM>
 static int backward_saved_x3(const crossclr_plan* plan, const Geo& g, const void* xhat, const void* stash, const float* rz, const float* wrz,
                              const float* k, float* gbuf, int accumulate, void* stream) {
-    const int NQ = 2 * plan->bpad / 32;
-    const int tps = (NQ + plan->bwd_slices - 1) / plan->bwd_slices;
-    const unsigned rb = 2 * plan->bpad / 64, nz = (unsigned)plan->bwd_slices;
-    dim3 block(256);
-#define CROSSCLR_LSX3(DC)                                                                                                                \
-    do {                                                                                                                                 \
-        if (k) LAUNCH((bwd_saved_x3_kernel<DC, true, RM>), dim3(rb, plan->Dpad / DC, nz), block, stream, (const x3_t*)xhat,             \
-                      (const float*)stash, g, rz, wrz, gbuf, accumulate, tps, k);                                                        \
-        else LAUNCH((bwd_saved_x3_kernel<DC, false, RM>), dim3(rb, plan->Dpad / DC, nz), block, stream, (const x3_t*)xhat,              \
-                    (const float*)stash, g, rz, wrz, gbuf, accumulate, tps, k);                                                          \
-    } while (0)
-    if (plan->Dpad % 256 == 0) CROSSCLR_LSX3(256);
-    else if (plan->Dpad % 128 == 0) CROSSCLR_LSX3(128);
-    else CROSSCLR_LSX3(64);
-#undef CROSSCLR_LSX3
+    const int tps = saved32_tps(plan, 2 * plan->bpad / 32);
+    saved32_with_dc(plan->Dpad, [&](auto dc) {
+        constexpr int DC = decltype(dc)::value;
+        if (k) LAUNCH((bwd_saved_x3_kernel<DC, true, RM>), saved32_grid(plan, DC), dim3(256), stream, (const x3_t*)xhat, (const float*)stash, g, rz,
+                      wrz, gbuf, accumulate, tps, k);
+        else LAUNCH((bwd_saved_x3_kernel<DC, false, RM>), saved32_grid(plan, DC), dim3(256), stream, (const x3_t*)xhat, (const float*)stash, g, rz,
+                    wrz, gbuf, accumulate, tps, k);
+    });
     return launch_status(RM ? "bwd_saved_x3_kernel (two-pass)" : "bwd_saved_x3_kernel");
+}
+// exact-fp32 plans: the saved backward over `ntiles` column tiles -- the local block (rzc / wrzc / kc unused) or, RECT, this rank's rows
+// against the gathered operand x with the gathered column statistics; single pass or two-pass (RM)
+template <bool RM, bool RECT>
+static int launch_saved32(const crossclr_plan* plan, const Geo& g, const void* x, const void* stash, const float* rz, const float* wrz,
+                          const float* rzc, const float* wrzc, const float* k, const float* kc, int ntiles, float* gbuf, int accumulate,
+                          void* stream) {
+    const int tps = saved32_tps(plan, ntiles);
+    saved32_with_dc(plan->Dpad, [&](auto dc) {
+        constexpr int DC = decltype(dc)::value;
+        if (k) LAUNCH((bwd_saved32_kernel<DC, true, RM, RECT>), saved32_grid(plan, DC), dim3(256), stream, (const float*)x, (const float*)stash, g,
+                      rz, wrz, gbuf, accumulate, tps, k, rzc, wrzc, kc);
+        else LAUNCH((bwd_saved32_kernel<DC, false, RM, RECT>), saved32_grid(plan, DC), dim3(256), stream, (const float*)x, (const float*)stash, g,
+                    rz, wrz, gbuf, accumulate, tps, k, rzc, wrzc, kc);
+    });
+    return launch_status(RECT ? (RM ? "bwd_saved32_kernel (rect, two-pass)" : "bwd_saved32_kernel (rect)")
+                              : (RM ? "bwd_saved32_kernel (two-pass)" : "bwd_saved32_kernel"));
+}
+
+// The two-pass regime's W = U rz_p + Ut rz_q as two launches of the bf16 saved backward: the rows' side weighs with the ROW statistics only
+// (columns' side: zeros), the columns' side with the COLUMN statistics only (rows' side: zeros) and accumulates
+struct SavedSide { SavedBlock block; const Geo& g; const void* stash; const char* what; };
+static int saved_two_pass(const crossclr_plan* plan, const void* x, const SavedSide& rows, const SavedSide& cols, const float* zeros,
+                          const float* rz_rows, const float* wrz_rows, const float* rz_cols, const float* wrz_cols, const float* krows,
+                          const float* kcols, float* gbuf, int accumulate, const char* label, void* stream) {
+    int rc = fast_backward_saved({rows.block, SavedOperand::RowMajor}, plan, rows.g, x, rows.stash, rz_rows, wrz_rows, zeros, zeros, gbuf,
+                                 accumulate, krows, kcols, stream);
+    if (rc) return fail(rc, "fast_backward_saved (%s): unsupported Dpad %d", rows.what, plan->Dpad);
+    rc = fast_backward_saved({cols.block, SavedOperand::RowMajor}, plan, cols.g, x, cols.stash, zeros, zeros, rz_cols, wrz_cols, gbuf, 1, krows,
+                             kcols, stream);
+    return rc ? fail(rc, "fast_backward_saved (%s): unsupported Dpad %d", cols.what, plan->Dpad) : launch_status(label);
+}
+// the Geo of a SavedBlock::RectTransposed launch: `segments` rank segments per row of the rectangular stash, the output rows (rank `row_rank`)
+// at segment `which` of it, the columns = this rank's own rows
+static Geo transposed_geo(const crossclr_plan* plan, Geo g, int segments, int which, int row_rank) {
+    g.col_ranks = segments; g.skip_rank = which; g.col_rank0 = plan->rank; g.col_wrap = 0; g.row_rank = row_rank;
+    return g;
 }
 #endif
 
+// what the saved backwards of the LOCAL block share: the sample weights (the rows' and the columns' negative scales are one array) and the
+// geometry; two_pass: per-row shifts allowed
+static int local_saved_args(const crossclr_plan* plan, const crossclr_sample_weights* sw, float temperature, float negative_weight,
+                            bool two_pass, const float** k, Geo* g) {
+    const float* kcols;
+    if (int rk = unpack_k(sw, k, &kcols)) return rk;
+    if (*k != kcols) return fail(CROSSCLR_E_ARG, "the local block's row and column negative scales are the same array");
+    return make_geo(plan, 1, plan->rank, -1, temperature, negative_weight, g, two_pass);
+}
+
+// crossclr_backward_saved (RowMajor), _saved_xf (FragmentOne) and _saved_xfp (FragmentPair); fn: the entry point's name, for its refusals
+static int backward_saved_local(const char* fn, SavedOperand operand, const crossclr_plan* plan, const void* x, const void* stash,
+                                float temperature, float negative_weight, const float* rz, const float* wrz,
+                                const crossclr_sample_weights* sw, float* gbuf, int accumulate, void* stream) {
+    if (!plan || !x || !stash || !rz || !wrz || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
+#ifdef CROSSCLR_NO_FAST
+    return fail(CROSSCLR_E_ARG, "%s needs the register-resident path", fn);
+#else
+    const bool row_major = operand == SavedOperand::RowMajor, pair = operand == SavedOperand::FragmentPair;
+    if (row_major && !plan->stash_bytes) return fail(CROSSCLR_E_ARG, "this plan has no save-for-backward path (stash_bytes == 0)");
+    if (!row_major && (!plan->stash_bytes || !plan->xf_bytes))
+        return fail(CROSSCLR_E_ARG, "this plan has no fragment-major saved backward (stash_bytes / xf_bytes == 0)");
+    if (pair && plan->stash_bytes >= ((size_t)1 << 32))
+        return fail(CROSSCLR_E_ARG, "%s addresses the saved exponentials with 32-bit offsets (stash of %zu bytes): use crossclr_backward_saved_xf", fn, plan->stash_bytes);
+    const float* k;
+    Geo g;
+    int rc = local_saved_args(plan, sw, temperature, negative_weight, false, &k, &g);
+    if (rc) return rc;
+    if (row_major && is_x3(plan)) return backward_saved_x3<false>(plan, g, x, stash, rz, wrz, k, gbuf, accumulate, stream);
+    if (row_major && !plan->fast_path && plan->mode == CROSSCLR_MODE_FP32)   // exact-fp32 mode
+        return launch_saved32<false, false>(plan, g, x, stash, rz, wrz, kNoF, kNoF, k, kNoF, 2 * plan->bpad / 32, gbuf, accumulate, stream);
+    rc = fast_backward_saved({SavedBlock::Local, operand}, plan, g, x, stash, rz, wrz, rz, wrz, gbuf, accumulate, k, k, stream);
+    if (rc) return fail(rc, "fast_backward_saved%s: unsupported Dpad %d", row_major ? "" : (pair ? " (xfp)" : " (xf)"), plan->Dpad);
+    return launch_status(row_major ? "fast_bwd_dsl_kernel" : (pair ? "fast_bwd_xfp_kernel" : "fast_bwd_dsl_kernel (xf)"));
+#endif
+}
 extern "C" int crossclr_backward_saved(const crossclr_plan* plan, const void* xhat, const void* stash, float temperature,
                                        float negative_weight, const float* rz, const float* wrz,
                                        const crossclr_sample_weights* sw, float* gbuf, int accumulate, void* stream) {
-    if (!plan || !xhat || !stash || !rz || !wrz || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "crossclr_backward_saved needs the register-resident path");
-#else
-    if (!plan->stash_bytes) return fail(CROSSCLR_E_ARG, "this plan has no save-for-backward path (stash_bytes == 0)");
-    const float *krows, *kcols;
-    if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
-    if (krows != kcols) return fail(CROSSCLR_E_ARG, "the local block's row and column negative scales are the same array");
-    Geo g;
-    int rc = make_geo(plan, 1, plan->rank, -1, temperature, negative_weight, &g);
-    if (rc) return rc;
-    if (is_x3(plan)) return backward_saved_x3<false>(plan, g, xhat, stash, rz, wrz, krows, gbuf, accumulate, stream);
-    if (!plan->fast_path && plan->mode == CROSSCLR_MODE_FP32) {   // exact-fp32 mode
-        const int NQ = 2 * plan->bpad / 32;
-        const int tps = (NQ + plan->bwd_slices - 1) / plan->bwd_slices;
-        const unsigned rb = 2 * plan->bpad / 64, nz = (unsigned)plan->bwd_slices;
-        dim3 block(256);
-#define CROSSCLR_LS32(DC)                                                                                                              \
-    do {                                                                                                                               \
-        if (krows) LAUNCH((bwd_saved32_kernel<DC, true>), dim3(rb, plan->Dpad / DC, nz), block, stream, (const float*)xhat,            \
-                          (const float*)stash, g, rz, wrz, gbuf, accumulate, tps, krows, kNoF, kNoF, kNoF);                                               \
-        else LAUNCH((bwd_saved32_kernel<DC, false>), dim3(rb, plan->Dpad / DC, nz), block, stream, (const float*)xhat,                 \
-                    (const float*)stash, g, rz, wrz, gbuf, accumulate, tps, krows, kNoF, kNoF, kNoF);                                                     \
-    } while (0)
-        if (plan->Dpad % 256 == 0) CROSSCLR_LS32(256);
-        else if (plan->Dpad % 128 == 0) CROSSCLR_LS32(128);
-        else CROSSCLR_LS32(64);
-#undef CROSSCLR_LS32
-        return launch_status("bwd_saved32_kernel");
-    }
-    rc = fast_backward_saved(plan, g, xhat, stash, rz, wrz, rz, wrz, gbuf, accumulate, krows, krows, 0, stream);
-    return rc ? fail(rc, "fast_backward_saved: unsupported Dpad %d", plan->Dpad) : launch_status("fast_bwd_dsl_kernel");
-#endif
+    return backward_saved_local("crossclr_backward_saved", SavedOperand::RowMajor, plan, xhat, stash, temperature, negative_weight, rz, wrz, sw,
+                                gbuf, accumulate, stream);
 }
-
 extern "C" int crossclr_backward_saved_xf(const crossclr_plan* plan, const void* xhat_xf, const void* stash, float temperature,
                                           float negative_weight, const float* rz, const float* wrz,
                                           const crossclr_sample_weights* sw, float* gbuf, int accumulate, void* stream) {
-    if (!plan || !xhat_xf || !stash || !rz || !wrz || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "crossclr_backward_saved_xf needs the register-resident path");
-#else
-    if (!plan->stash_bytes || !plan->xf_bytes) return fail(CROSSCLR_E_ARG, "this plan has no fragment-major saved backward (stash_bytes / xf_bytes == 0)");
-    const float *krows, *kcols;
-    if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
-    if (krows != kcols) return fail(CROSSCLR_E_ARG, "the local block's row and column negative scales are the same array");
-    Geo g;
-    int rc = make_geo(plan, 1, plan->rank, -1, temperature, negative_weight, &g);
-    if (rc) return rc;
-    rc = fast_backward_saved(plan, g, xhat_xf, stash, rz, wrz, rz, wrz, gbuf, accumulate, krows, krows, 3, stream);
-    return rc ? fail(rc, "fast_backward_saved (xf): unsupported Dpad %d", plan->Dpad) : launch_status("fast_bwd_dsl_kernel (xf)");
-#endif
+    return backward_saved_local("crossclr_backward_saved_xf", SavedOperand::FragmentOne, plan, xhat_xf, stash, temperature, negative_weight, rz,
+                                wrz, sw, gbuf, accumulate, stream);
 }
-
 extern "C" int crossclr_backward_saved_xfp(const crossclr_plan* plan, const void* xhat_xf, const void* stash, float temperature,
                                            float negative_weight, const float* rz, const float* wrz,
                                            const crossclr_sample_weights* sw, float* gbuf, int accumulate, void* stream) {
-    if (!plan || !xhat_xf || !stash || !rz || !wrz || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "crossclr_backward_saved_xfp needs the register-resident path");
-#else
-    if (!plan->stash_bytes || !plan->xf_bytes) return fail(CROSSCLR_E_ARG, "this plan has no fragment-major saved backward (stash_bytes / xf_bytes == 0)");
-    if (plan->stash_bytes >= ((size_t)1 << 32))
-        return fail(CROSSCLR_E_ARG, "crossclr_backward_saved_xfp addresses the saved exponentials with 32-bit offsets (stash of %zu bytes): use crossclr_backward_saved_xf", plan->stash_bytes);
-    const float *krows, *kcols;
-    if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
-    if (krows != kcols) return fail(CROSSCLR_E_ARG, "the local block's row and column negative scales are the same array");
-    Geo g;
-    int rc = make_geo(plan, 1, plan->rank, -1, temperature, negative_weight, &g);
-    if (rc) return rc;
-    rc = fast_backward_saved(plan, g, xhat_xf, stash, rz, wrz, rz, wrz, gbuf, accumulate, krows, krows, 4, stream);
-    return rc ? fail(rc, "fast_backward_saved (xfp): unsupported Dpad %d", plan->Dpad) : launch_status("fast_bwd_xfp_kernel");
-#endif
+    return backward_saved_local("crossclr_backward_saved_xfp", SavedOperand::FragmentPair, plan, xhat_xf, stash, temperature, negative_weight, rz,
+                                wrz, sw, gbuf, accumulate, stream);
 }
 
 extern "C" int crossclr_forward_pairs(const crossclr_plan* plan, const void* xhat_rows, const void* xhat_all, int first_rank,
@@ -1030,53 +1047,29 @@ extern "C" int crossclr_backward_saved_s(const crossclr_plan* plan, const void* 
                                          const crossclr_sample_weights* sw, float* gbuf, int accumulate, void* stream) {
     if (!plan || !xhat || !stash || !rz || !wrz || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
     if (!stash_bytes_s(plan)) return fail(CROSSCLR_E_ARG, "this plan has no two-pass save-for-backward path (crossclr_stash_bytes_s == 0)");
-    const float *krows, *kcols;
-    if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
-    if (krows != kcols) return fail(CROSSCLR_E_ARG, "the local block's row and column negative scales are the same array");
+    const float* k;
     Geo g;
-    int rc = make_geo(plan, 1, plan->rank, -1, temperature, negative_weight, &g, true);
+    int rc = local_saved_args(plan, sw, temperature, negative_weight, true, &k, &g);
     if (rc) return rc;
 #ifndef CROSSCLR_NO_FAST
     if (plan->mode == CROSSCLR_MODE_BF16) {
-        // W[p][q] = U[p][q] rz_p + U[q][p] rz_q: the direct launch weighs with the ROW statistics only (column side: zeros), the transposed
-        // launch with the statistics of the rows it contracts over (output side: zeros) and accumulates -- two 8 B^2 D launches of the saved
-        // backward instead of the 16 B^2 D (1 + ...) recompute of the generic kernel
-        if (wide_two_pass(plan)) {   // U rz_p from the first array, Ut rz_q from the second: two direct launches of the D-slice kernel in column parts
-            const unsigned char* U = static_cast<const unsigned char*>(stash);
-            const size_t rb = rect_bytes_s(plan);
-            const float* zw = reinterpret_cast<const float*>(U + 2 * rb);
-            rc = fast_backward_saved(plan, g, xhat, U, rz, wrz, zw, zw, gbuf, accumulate, krows, krows, 1, stream);
-            if (rc) return fail(rc, "fast_backward_saved (two-pass, wide, rows' side): unsupported Dpad %d", plan->Dpad);
-            rc = fast_backward_saved(plan, g, xhat, U + rb, zw, zw, rz, wrz, gbuf, 1, krows, krows, 1, stream);
-            return rc ? fail(rc, "fast_backward_saved (two-pass, wide, columns' side): unsupported Dpad %d", plan->Dpad)
-                      : launch_status("fast_bwd_dsl_kernel (two-pass pair, wide)");
-        }
-        const float* zeros = reinterpret_cast<const float*>(static_cast<const unsigned char*>(stash) + rect_bytes_s(plan));
-        rc = fast_backward_saved(plan, g, xhat, stash, rz, wrz, zeros, zeros, gbuf, accumulate, krows, krows, 1, stream);
-        if (rc) return fail(rc, "fast_backward_saved (two-pass, direct): unsupported Dpad %d", plan->Dpad);
-        Geo gt = g;
-        gt.col_ranks = 1; gt.skip_rank = 0; gt.col_rank0 = plan->rank; gt.col_wrap = 0; gt.row_rank = plan->rank;
-        rc = fast_backward_saved(plan, gt, xhat, stash, zeros, zeros, rz, wrz, gbuf, 1, krows, krows, 2, stream);
-        return rc ? fail(rc, "fast_backward_saved (two-pass, transposed): unsupported Dpad %d", plan->Dpad) : launch_status("fast_bwd_dsl_kernel (two-pass pair)");
+        // W[p][q] = U[p][q] rz_p + U[q][p] rz_q as two 8 B^2 D launches of the saved backward (saved_two_pass) instead of the
+        // 16 B^2 D (1 + ...) recompute of the generic kernel
+        const unsigned char* U = static_cast<const unsigned char*>(stash);
+        const size_t rb = rect_bytes_s(plan);
+        if (wide_two_pass(plan))     // U rz_p from the first array, Ut rz_q from the second: two direct launches of the D-slice kernel in column parts
+            return saved_two_pass(plan, xhat, {SavedBlock::Rect, g, U, "two-pass, wide, rows' side"},
+                                  {SavedBlock::Rect, g, U + rb, "two-pass, wide, columns' side"}, reinterpret_cast<const float*>(U + 2 * rb), rz,
+                                  wrz, rz, wrz, k, k, gbuf, accumulate, "fast_bwd_dsl_kernel (two-pass pair, wide)", stream);
+        // one array: the direct launch, then the transposed one with the statistics of the rows it contracts over
+        return saved_two_pass(plan, xhat, {SavedBlock::Rect, g, U, "two-pass, direct"},
+                              {SavedBlock::RectTransposed, transposed_geo(plan, g, 1, 0, plan->rank), U, "two-pass, transposed"},
+                              reinterpret_cast<const float*>(U + rb), rz, wrz, rz, wrz, k, k, gbuf, accumulate,
+                              "fast_bwd_dsl_kernel (two-pass pair)", stream);
     }
-    if (is_x3(plan)) return backward_saved_x3<true>(plan, g, xhat, stash, rz, wrz, krows, gbuf, accumulate, stream);
+    if (is_x3(plan)) return backward_saved_x3<true>(plan, g, xhat, stash, rz, wrz, k, gbuf, accumulate, stream);
 #endif
-    const int NQ = 2 * plan->bpad / 32;
-    const int tps = (NQ + plan->bwd_slices - 1) / plan->bwd_slices;
-    const unsigned rb = 2 * plan->bpad / 64, nz = (unsigned)plan->bwd_slices;
-    dim3 block(256);
-#define CROSSCLR_LS32R(DC)                                                                                                             \
-    do {                                                                                                                               \
-        if (krows) LAUNCH((bwd_saved32_kernel<DC, true, true>), dim3(rb, plan->Dpad / DC, nz), block, stream, (const float*)xhat,      \
-                          (const float*)stash, g, rz, wrz, gbuf, accumulate, tps, krows, kNoF, kNoF, kNoF);                                               \
-        else LAUNCH((bwd_saved32_kernel<DC, false, true>), dim3(rb, plan->Dpad / DC, nz), block, stream, (const float*)xhat,           \
-                    (const float*)stash, g, rz, wrz, gbuf, accumulate, tps, krows, kNoF, kNoF, kNoF);                                                     \
-    } while (0)
-    if (plan->Dpad % 256 == 0) CROSSCLR_LS32R(256);
-    else if (plan->Dpad % 128 == 0) CROSSCLR_LS32R(128);
-    else CROSSCLR_LS32R(64);
-#undef CROSSCLR_LS32R
-    return launch_status("bwd_saved32_kernel (two-pass)");
+    return launch_saved32<true, false>(plan, g, xhat, stash, rz, wrz, kNoF, kNoF, k, kNoF, 2 * plan->bpad / 32, gbuf, accumulate, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1249,6 +1242,13 @@ extern "C" int crossclr_forward_rect_save(const crossclr_plan* plan, const void*
 #endif
 }
 
+// what the saved backwards of a rectangular block share: the sample weights and the geometry of the rank range
+static int rect_saved_args(const crossclr_plan* plan, const crossclr_sample_weights* sw, int first_rank, int nranks, float temperature,
+                           float negative_weight, bool two_pass, const float** krows, const float** kcols, Geo* g) {
+    if (int rk = unpack_k(sw, krows, kcols)) return rk;
+    return rect_geo(plan, first_rank, nranks, temperature, negative_weight, g, two_pass);
+}
+
 extern "C" int crossclr_backward_rect_saved(const crossclr_plan* plan, const void* xhat_all, const void* stash, int first_rank,
                                             int nranks, float temperature, float negative_weight, const float* rz_rows,
                                             const float* wrz_rows, const float* rz_all, const float* wrz_all,
@@ -1258,37 +1258,18 @@ extern "C" int crossclr_backward_rect_saved(const crossclr_plan* plan, const voi
 #ifdef CROSSCLR_NO_FAST
     return fail(CROSSCLR_E_ARG, "crossclr_backward_rect_saved needs the register-resident path");
 #else
-    if (plan->stash_bytes && !plan->fast_path && plan->mode == CROSSCLR_MODE_FP32) {   // exact-fp32 plans: bwd_saved32_kernel<..., RECT>
-        const float *kr32, *kc32;
-        if (int rk = unpack_k(sw, &kr32, &kc32)) return rk;
-        Geo g32;
-        int rc32 = rect_geo(plan, first_rank, nranks, temperature, negative_weight, &g32);
-        if (rc32) return rc32;
-        const int NQ = nranks * (2 * plan->bpad / 32);
-        const int tps32 = (NQ + plan->bwd_slices - 1) / plan->bwd_slices;
-        const unsigned rb = 2 * plan->bpad / 64, nz = (unsigned)plan->bwd_slices;
-        dim3 block(256);
-#define CROSSCLR_LS32X(DC)                                                                                                                    \
-    do {                                                                                                                                      \
-        if (kr32) LAUNCH((bwd_saved32_kernel<DC, true, false, true>), dim3(rb, plan->Dpad / DC, nz), block, stream, (const float*)xhat_all,   \
-                         (const float*)stash, g32, rz_rows, wrz_rows, gbuf, accumulate, tps32, kr32, rz_all, wrz_all, kc32);                  \
-        else LAUNCH((bwd_saved32_kernel<DC, false, false, true>), dim3(rb, plan->Dpad / DC, nz), block, stream, (const float*)xhat_all,       \
-                    (const float*)stash, g32, rz_rows, wrz_rows, gbuf, accumulate, tps32, kr32, rz_all, wrz_all, kc32);                       \
-    } while (0)
-        if (plan->Dpad % 256 == 0) CROSSCLR_LS32X(256);
-        else if (plan->Dpad % 128 == 0) CROSSCLR_LS32X(128);
-        else CROSSCLR_LS32X(64);
-#undef CROSSCLR_LS32X
-        return launch_status("bwd_saved32_kernel (rect)");
-    }
-    if (!plan->stash_bytes || !(plan->fast_path || (plan->mode == CROSSCLR_MODE_BF16 && plan->Dpad > 1024)))
+    const bool exact = plan->stash_bytes && !plan->fast_path && plan->mode == CROSSCLR_MODE_FP32;   // exact-fp32 plans: bwd_saved32_kernel<..., RECT>
+    if (!exact && (!plan->stash_bytes || !(plan->fast_path || (plan->mode == CROSSCLR_MODE_BF16 && plan->Dpad > 1024))))
         return fail(CROSSCLR_E_ARG, "this plan has no save-for-backward path for remote blocks");
     const float *krows, *kcols;
-    if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
     Geo g;
-    int rc = rect_geo(plan, first_rank, nranks, temperature, negative_weight, &g);
+    int rc = rect_saved_args(plan, sw, first_rank, nranks, temperature, negative_weight, false, &krows, &kcols, &g);
     if (rc) return rc;
-    rc = fast_backward_saved(plan, g, xhat_all, stash, rz_rows, wrz_rows, rz_all, wrz_all, gbuf, accumulate, krows, kcols, 1, stream);
+    if (exact)
+        return launch_saved32<false, true>(plan, g, xhat_all, stash, rz_rows, wrz_rows, rz_all, wrz_all, krows, kcols,
+                                           nranks * (2 * plan->bpad / 32), gbuf, accumulate, stream);
+    rc = fast_backward_saved({SavedBlock::Rect, SavedOperand::RowMajor}, plan, g, xhat_all, stash, rz_rows, wrz_rows, rz_all, wrz_all, gbuf,
+                             accumulate, krows, kcols, stream);
     return rc ? fail(rc, "fast_backward_saved: unsupported Dpad %d", plan->Dpad) : launch_status("fast_bwd_dsl_kernel (rect)");
 #endif
 }
@@ -1339,40 +1320,22 @@ extern "C" int crossclr_backward_rect_saved_s(const crossclr_plan* plan, const v
     if (!crossclr_rect_stash_bytes_s(plan, nranks))
         return fail(CROSSCLR_E_ARG, "this plan has no two-pass save-for-backward path for remote blocks (crossclr_rect_stash_bytes_s == 0)");
     const float *krows, *kcols;
-    if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
     Geo g;
-    int rc = rect_geo(plan, first_rank, nranks, temperature, negative_weight, &g, true);
+    int rc = rect_saved_args(plan, sw, first_rank, nranks, temperature, negative_weight, true, &krows, &kcols, &g);
     if (rc) return rc;
 #ifndef CROSSCLR_NO_FAST
     if (plan->mode == CROSSCLR_MODE_BF16) {
-        // W[p][q] = U[p][q] rz_p + Ut[p][q] rz_q: the launch over U weighs with the ROW statistics only (column side: zeros), the launch over Ut
-        // with the COLUMN statistics only (row side: zeros) and accumulates -- two rectangular launches of the saved backward, no recompute
+        // W[p][q] = U[p][q] rz_p + Ut[p][q] rz_q: two rectangular launches of the saved backward (saved_two_pass), no recompute
         const size_t one = crossclr_rect_stash_bytes(plan, nranks);
         const unsigned char* U = static_cast<const unsigned char*>(stash);
         const float* zeros = reinterpret_cast<const float*>(U + 2 * one);       // [world][2 bpad] for the column side, [2 bpad] of it for the rows
-        rc = fast_backward_saved(plan, g, xhat_all, U, rz_rows, wrz_rows, zeros, zeros, gbuf, accumulate, krows, kcols, 1, stream);
-        if (rc) return fail(rc, "fast_backward_saved (two-pass, rows' side): unsupported Dpad %d", plan->Dpad);
-        rc = fast_backward_saved(plan, g, xhat_all, U + one, zeros, zeros, rz_all, wrz_all, gbuf, 1, krows, kcols, 1, stream);
-        return rc ? fail(rc, "fast_backward_saved (two-pass, columns' side): unsupported Dpad %d", plan->Dpad)
-                  : launch_status("fast_bwd_dsl_kernel (rect, two-pass pair)");
+        return saved_two_pass(plan, xhat_all, {SavedBlock::Rect, g, U, "two-pass, rows' side"},
+                              {SavedBlock::Rect, g, U + one, "two-pass, columns' side"}, zeros, rz_rows, wrz_rows, rz_all, wrz_all, krows, kcols,
+                              gbuf, accumulate, "fast_bwd_dsl_kernel (rect, two-pass pair)", stream);
     }
 #endif
-    const int NQ = nranks * (2 * plan->bpad / 32);
-    const int tps = (NQ + plan->bwd_slices - 1) / plan->bwd_slices;
-    const unsigned rb = 2 * plan->bpad / 64, nz = (unsigned)plan->bwd_slices;
-    dim3 block(256);
-#define CROSSCLR_LS32XS(DC)                                                                                                                  \
-    do {                                                                                                                                     \
-        if (krows) LAUNCH((bwd_saved32_kernel<DC, true, true, true>), dim3(rb, plan->Dpad / DC, nz), block, stream, (const float*)xhat_all,  \
-                          (const float*)stash, g, rz_rows, wrz_rows, gbuf, accumulate, tps, krows, rz_all, wrz_all, kcols);                  \
-        else LAUNCH((bwd_saved32_kernel<DC, false, true, true>), dim3(rb, plan->Dpad / DC, nz), block, stream, (const float*)xhat_all,       \
-                    (const float*)stash, g, rz_rows, wrz_rows, gbuf, accumulate, tps, krows, rz_all, wrz_all, kcols);                        \
-    } while (0)
-    if (plan->Dpad % 256 == 0) CROSSCLR_LS32XS(256);
-    else if (plan->Dpad % 128 == 0) CROSSCLR_LS32XS(128);
-    else CROSSCLR_LS32XS(64);
-#undef CROSSCLR_LS32XS
-    return launch_status("bwd_saved32_kernel (rect, two-pass)");
+    return launch_saved32<true, true>(plan, g, xhat_all, stash, rz_rows, wrz_rows, rz_all, wrz_all, krows, kcols, nranks * (2 * plan->bpad / 32),
+                                      gbuf, accumulate, stream);
 }
 
 
@@ -1405,72 +1368,60 @@ extern "C" int crossclr_backward_rect_saved_xfp(const crossclr_plan* plan, const
     if ((size_t)plan->world * plan->operand_bytes >= ((size_t)1 << 32) || fast_stash_bytes_rect(plan->bpad, plan->Dpad, nranks) >= ((size_t)1 << 32))
         return fail(CROSSCLR_E_ARG, "crossclr_backward_rect_saved_xfp uses 32-bit offsets (operand / stash of 4 GiB or more): use crossclr_backward_rect_saved");
     const float *krows, *kcols;
-    if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
     Geo g;
-    int rc = rect_geo(plan, first_rank, nranks, temperature, negative_weight, &g);
+    int rc = rect_saved_args(plan, sw, first_rank, nranks, temperature, negative_weight, false, &krows, &kcols, &g);
     if (rc) return rc;
-    rc = fast_backward_saved(plan, g, xf_all, stash, rz_rows, wrz_rows, rz_all, wrz_all, gbuf, accumulate, krows, kcols, 5, stream);
+    rc = fast_backward_saved({SavedBlock::Rect, SavedOperand::FragmentPair}, plan, g, xf_all, stash, rz_rows, wrz_rows, rz_all, wrz_all, gbuf,
+                             accumulate, krows, kcols, stream);
     return rc ? fail(rc, "fast_backward_saved (xfp, rect): unsupported Dpad %d", plan->Dpad) : launch_status("fast_bwd_xfp_kernel (rect)");
 #endif
 }
 
-// crossclr_backward_rect_saved_t on this rank's LOCAL fragment-major operand (what crossclr_normalize_xf wrote), with the pair kernel.
+// The transpose of one saved rectangular block: what block (this rank x partner) contributes to the PARTNER's gradient buffer.
+// crossclr_backward_rect_saved_t (RowMajor: this rank's packed operand) and _t_xfp (FragmentPair: its LOCAL fragment-major operand, what
+// crossclr_normalize_xf wrote, with the pair kernel); fn: the entry point's name, for its refusals
+static int backward_rect_saved_t(const char* fn, SavedOperand operand, const crossclr_plan* plan, const void* x_rows, const void* stash,
+                                 int first_rank, int nranks, int which, float temperature, float negative_weight, const float* rz_rows,
+                                 const float* wrz_rows, const float* rz_all, const float* wrz_all, const crossclr_sample_weights* sw,
+                                 float* gpartner, void* stream) {
+    if (!plan || !x_rows || !stash || !rz_rows || !wrz_rows || !rz_all || !wrz_all || !gpartner) return fail(CROSSCLR_E_ARG, "NULL argument");
+#ifdef CROSSCLR_NO_FAST
+    return fail(CROSSCLR_E_ARG, "%s needs the register-resident path", fn);
+#else
+    const bool pair = operand == SavedOperand::FragmentPair;
+    if (!plan->stash_bytes || !plan->fast_path || (pair && !plan->xf_bytes))
+        return fail(CROSSCLR_E_ARG, pair ? "this plan has no fragment-major saved backward for remote blocks"
+                                         : "this plan has no save-for-backward path for remote blocks");
+    if (which < 0 || which >= nranks) return fail(CROSSCLR_E_ARG, "which must be 0 .. nranks-1");
+    if (pair && fast_stash_bytes_rect(plan->bpad, plan->Dpad, nranks) >= ((size_t)1 << 32))
+        return fail(CROSSCLR_E_ARG, "%s uses 32-bit offsets (stash of 4 GiB or more): use crossclr_backward_rect_saved_t", fn);
+    const float *krows, *kcols;
+    Geo g;
+    int rc = rect_saved_args(plan, sw, first_rank, nranks, temperature, negative_weight, false, &krows, &kcols, &g);     // (validates the range; scales)
+    if (rc) return rc;
+    // the kernel sees: rows = the partner's 2 bpad rows (statistics: its segment of the gathered arrays), columns = this rank's own rows
+    const int partner = (first_rank + which) % plan->world;
+    const size_t n2 = (size_t)2 * plan->bpad;
+    rc = fast_backward_saved({SavedBlock::RectTransposed, operand}, plan, transposed_geo(plan, g, nranks, which, partner), x_rows, stash,
+                             rz_all + partner * n2, wrz_all + partner * n2, rz_rows, wrz_rows, gpartner, 0,
+                             kcols ? kcols + partner * n2 : nullptr, krows, stream);
+    if (rc) return fail(rc, "fast_backward_saved%s: unsupported Dpad %d", pair ? " (xfp, transposed)" : "", plan->Dpad);
+    return launch_status(pair ? "fast_bwd_xfp_kernel (rect, transposed)" : "fast_bwd_dsl_kernel (rect, transposed)");
+#endif
+}
 extern "C" int crossclr_backward_rect_saved_t_xfp(const crossclr_plan* plan, const void* xf_rows, const void* stash, int first_rank,
                                                   int nranks, int which, float temperature, float negative_weight, const float* rz_rows,
                                                   const float* wrz_rows, const float* rz_all, const float* wrz_all,
                                                   const crossclr_sample_weights* sw, float* gpartner, void* stream) {
-    if (!plan || !xf_rows || !stash || !rz_rows || !wrz_rows || !rz_all || !wrz_all || !gpartner) return fail(CROSSCLR_E_ARG, "NULL argument");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "crossclr_backward_rect_saved_t_xfp needs the register-resident path");
-#else
-    if (!plan->stash_bytes || !plan->fast_path || !plan->xf_bytes) return fail(CROSSCLR_E_ARG, "this plan has no fragment-major saved backward for remote blocks");
-    if (which < 0 || which >= nranks) return fail(CROSSCLR_E_ARG, "which must be 0 .. nranks-1");
-    if (fast_stash_bytes_rect(plan->bpad, plan->Dpad, nranks) >= ((size_t)1 << 32))
-        return fail(CROSSCLR_E_ARG, "crossclr_backward_rect_saved_t_xfp uses 32-bit offsets (stash of 4 GiB or more): use crossclr_backward_rect_saved_t");
-    const float *krows, *kcols;
-    if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
-    Geo g;
-    int rc = rect_geo(plan, first_rank, nranks, temperature, negative_weight, &g);     // (validates the range; scales)
-    if (rc) return rc;
-    const int partner = (first_rank + which) % plan->world;
-    const size_t n2 = (size_t)2 * plan->bpad;
-    g.col_ranks = nranks;        // rank segments per row of the rectangular stash
-    g.skip_rank = which;         // the partner's segment inside a stash row
-    g.col_rank0 = plan->rank; g.col_wrap = 0;
-    g.row_rank = partner;
-    rc = fast_backward_saved(plan, g, xf_rows, stash, rz_all + partner * n2, wrz_all + partner * n2, rz_rows, wrz_rows, gpartner, 0,
-                             kcols ? kcols + partner * n2 : nullptr, krows, 6, stream);
-    return rc ? fail(rc, "fast_backward_saved (xfp, transposed): unsupported Dpad %d", plan->Dpad) : launch_status("fast_bwd_xfp_kernel (rect, transposed)");
-#endif
+    return backward_rect_saved_t("crossclr_backward_rect_saved_t_xfp", SavedOperand::FragmentPair, plan, xf_rows, stash, first_rank, nranks, which,
+                                 temperature, negative_weight, rz_rows, wrz_rows, rz_all, wrz_all, sw, gpartner, stream);
 }
-
-// The transpose of one saved rectangular block: what block (this rank x partner) contributes to the PARTNER's gradient buffer.
 extern "C" int crossclr_backward_rect_saved_t(const crossclr_plan* plan, const void* xhat_rows, const void* stash, int first_rank,
                                               int nranks, int which, float temperature, float negative_weight, const float* rz_rows,
                                               const float* wrz_rows, const float* rz_all, const float* wrz_all,
                                               const crossclr_sample_weights* sw, float* gpartner, void* stream) {
-    if (!plan || !xhat_rows || !stash || !rz_rows || !wrz_rows || !rz_all || !wrz_all || !gpartner) return fail(CROSSCLR_E_ARG, "NULL argument");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "crossclr_backward_rect_saved_t needs the register-resident path");
-#else
-    if (!plan->stash_bytes || !plan->fast_path) return fail(CROSSCLR_E_ARG, "this plan has no save-for-backward path for remote blocks");
-    if (which < 0 || which >= nranks) return fail(CROSSCLR_E_ARG, "which must be 0 .. nranks-1");
-    const float *krows, *kcols;
-    if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
-    Geo g;
-    int rc = rect_geo(plan, first_rank, nranks, temperature, negative_weight, &g);     // (validates the range; scales)
-    if (rc) return rc;
-    const int partner = (first_rank + which) % plan->world;
-    const size_t n2 = (size_t)2 * plan->bpad;
-    // the kernel sees: rows = the partner's 2 bpad rows (statistics: its segment of the gathered arrays), columns = this rank's own rows
-    g.col_ranks = nranks;        // rank segments per row of the rectangular stash
-    g.skip_rank = which;         // the partner's segment inside a stash row
-    g.col_rank0 = plan->rank; g.col_wrap = 0;
-    g.row_rank = partner;
-    rc = fast_backward_saved(plan, g, xhat_rows, stash, rz_all + partner * n2, wrz_all + partner * n2, rz_rows, wrz_rows, gpartner, 0,
-                             kcols ? kcols + partner * n2 : nullptr, krows, 2, stream);
-    return rc ? fail(rc, "fast_backward_saved: unsupported Dpad %d", plan->Dpad) : launch_status("fast_bwd_dsl_kernel (rect, transposed)");
-#endif
+    return backward_rect_saved_t("crossclr_backward_rect_saved_t", SavedOperand::RowMajor, plan, xhat_rows, stash, first_rank, nranks, which,
+                                 temperature, negative_weight, rz_rows, wrz_rows, rz_all, wrz_all, sw, gpartner, stream);
 }
 
 // the recomputing backward over a (wrapping) rank range of the whole gathered operand: the blocks OTHER ranks evaluated in the

@@ -944,52 +944,96 @@ static inline int fast_forward_save(const crossclr_plan* p, const Geo& g, const 
     const FwdWork wk = fast_forward_work(p, 1, -1, true);
     return fast_forward_pipe(p, g, wk, x, x, part, colpart, header, 1, ks, ks, stash, stream);
 }
-// mode 0: the symmetric local block (x is both operands).  mode 1: a rectangular block whose forward saved its exponentials (g describes
-// the column ranks; cols / rz_cols / wrz_cols / kc use the column operand's indexing).  mode 2: the transpose of ONE rectangular block
-// (crossclr_backward_rect_saved_t): output rows = the partner's, cols / *_cols / kc = this rank's LOCAL operand and statistics,
-// rz / wrz / ks = the partner's statistics; g.col_ranks = rank segments per stash row, g.skip_rank = the partner's segment.
+// One launch of a saved backward is named by two enums.
+// SavedBlock -- which block of the similarity matrix the saved exponentials cover (its value is the kernels' MODE template argument):
+//   Local: the symmetric local block (cols is both operands).  Rect: a rectangular block whose forward saved its exponentials (g describes
+//   the column ranks; cols / rz_cols / wrz_cols / kc use the column operand's indexing).  RectTransposed: the transpose of ONE rectangular
+//   block (crossclr_backward_rect_saved_t): output rows = the partner's, cols / *_cols / kc = this rank's LOCAL operand and statistics,
+//   rz / wrz / ks = the partner's statistics; g.col_ranks = rank segments per stash row, g.skip_rank = the partner's segment.
+// SavedOperand -- the layout of cols and with it the kernel: RowMajor: the packed operand, column tiles staged through LDS.  FragmentOne: the
+//   fragment-major copy, one tile per barrier interval (Local only).  FragmentPair: the fragment-major copy with the pair kernel
+//   (crossclr_kernels_dslp.h; stash below 4 GiB: 32-bit scalar offsets).
+enum class SavedBlock { Local = 0, Rect = 1, RectTransposed = 2 };
+enum class SavedOperand { RowMajor, FragmentOne, FragmentPair };
+struct SavedKind { SavedBlock block; SavedOperand operand; };
 struct SavedLaunch {      // one launch of a saved backward, as the leaves below take it
     const crossclr_plan* p; Geo g; const void* cols; const void* stash; const float *rz, *wrz, *rz_cols, *wrz_cols; float* gbuf; int accumulate;
-    const float *ks, *kc; int mode; int tps; void* stream; size_t stash_bytes;
+    const float *ks, *kc; SavedKind kind; int tps; void* stream; size_t stash_bytes;
 };
-// the pair kernel (crossclr_kernels_dslp.h): local block, fragment-major operand, two tiles per barrier interval
+
+// Dpad -> the instantiation of a saved backward kernel: DK 16-element steps per row of the (part of the) operand a block multiplies, XP column
+// parts of Dpad / XP (blockIdx.z: XP is also the grid's z extent), TPRF tiles per row block of the forward that saved the exponentials.
+// f(SavedShape<...>()) launches the row of the table; a Dpad outside it is refused.
+template <int DK_, int XP_, int TPRF_> struct SavedShape { static constexpr int DK = DK_, XP = XP_, TPRF = TPRF_; };
+template <class F> static inline int saved_shape(int Dpad, F f) {            // launch_saved_lds / _xf1 / _xfp
+    switch (Dpad) {
+        case 128: return f(SavedShape<8, 1, 8>());
+        case 256: return f(SavedShape<16, 1, 8>());
+        case 384: return f(SavedShape<24, 1, 8>());
+        case 512: return f(SavedShape<32, 1, 8>());
+        case 768: return f(SavedShape<24, 2, 4>());
+        case 1024: return f(SavedShape<32, 2, 4>());
+        default: return CROSSCLR_E_ARG;
+    }
+}
+template <class F> static inline int saved_shape_wide(int Dpad, F f) {       // launch_saved_wide / _wide_xfp
+    switch (Dpad) {
+        case 1152: return f(SavedShape<24, 3, 4>());
+        case 1536: return f(SavedShape<32, 3, 4>());
+        case 2048: return f(SavedShape<32, 4, 4>());
+        case 2560: return f(SavedShape<32, 5, 4>());
+        case 3072: return f(SavedShape<32, 6, 4>());
+        case 4096: return f(SavedShape<32, 8, 4>());
+        case 5120: return f(SavedShape<32, 10, 4>());
+        case 6144: return f(SavedShape<32, 12, 4>());
+        case 8192: return f(SavedShape<32, 16, 4>());
+        default: return CROSSCLR_E_ARG;
+    }
+}
+
+// The instantiation for (shape, sample weights, block).  NB: how many of the blocks Local, Rect, RectTransposed the calling leaf launches (a
+// leaf instantiates no kernel it cannot reach); a block beyond them has no kernel.
+typedef void (*SavedDslKernel)(const bf16_t*, const unsigned char*, Geo, const float*, const float*, const float*, const float*, float*, int, int,
+                               const float*, const float*);
+typedef void (*SavedXfpKernel)(const unsigned char*, const unsigned char*, unsigned, Geo, const float*, const float*, const float*, const float*,
+                               float*, int, int, const float*, const float*);
+template <class S, bool SW, int NB, bool XF> static inline SavedDslKernel saved_dsl_kernel(SavedBlock b) {
+    if (b == SavedBlock::Local) return fast_bwd_dsl_kernel<S::DK, SW, 0, S::XP, S::TPRF, XF>;
+    if constexpr (NB > 1) if (b == SavedBlock::Rect) return fast_bwd_dsl_kernel<S::DK, SW, 1, S::XP, S::TPRF, XF>;
+    if constexpr (NB > 2) if (b == SavedBlock::RectTransposed) return fast_bwd_dsl_kernel<S::DK, SW, 2, S::XP, S::TPRF, XF>;
+    return nullptr;
+}
+template <class S, bool SW, int NB> static inline SavedXfpKernel saved_xfp_kernel(SavedBlock b) {
+    if (b == SavedBlock::Local) return fast_bwd_xfp_kernel<S::DK, SW, 0, S::XP, S::TPRF>;
+    if constexpr (NB > 1) if (b == SavedBlock::Rect) return fast_bwd_xfp_kernel<S::DK, SW, 1, S::XP, S::TPRF>;
+    if constexpr (NB > 2) if (b == SavedBlock::RectTransposed) return fast_bwd_xfp_kernel<S::DK, SW, 2, S::XP, S::TPRF>;
+    return nullptr;
+}
+// a SavedLaunch in the kernel's argument order, over (128-row blocks) x slices x column parts thread blocks
+static inline int saved_launch(SavedDslKernel kernel, const SavedLaunch& a, int parts) {
+    if (!kernel) return CROSSCLR_E_ARG;
+    CROSSCLR_FAST_LAUNCH(kernel, dim3(2 * a.p->bpad / 128, a.p->bwd_slices, parts), dim3(256), a.stream, (const bf16_t*)a.cols,
+                         (const unsigned char*)a.stash, a.g, a.rz, a.wrz, a.rz_cols, a.wrz_cols, a.gbuf, a.accumulate, a.tps, a.ks, a.kc);
+    return CROSSCLR_OK;
+}
+static inline int saved_launch(SavedXfpKernel kernel, const SavedLaunch& a, int parts) {
+    if (!kernel) return CROSSCLR_E_ARG;
+    CROSSCLR_FAST_LAUNCH(kernel, dim3(2 * a.p->bpad / 128, a.p->bwd_slices, parts), dim3(256), a.stream, (const unsigned char*)a.cols,
+                         (const unsigned char*)a.stash, (unsigned)a.stash_bytes, a.g, a.rz, a.wrz, a.rz_cols, a.wrz_cols, a.gbuf, a.accumulate,
+                         a.tps, a.ks, a.kc);
+    return CROSSCLR_OK;
+}
+
+// the pair kernel (crossclr_kernels_dslp.h): fragment-major operand, two tiles per barrier interval; all three blocks
 #ifndef CROSSCLR_DEF_SAVED_XFP
 int launch_saved_xfp(const SavedLaunch& a);
 #else
 CROSSCLR_LEAF int launch_saved_xfp(const SavedLaunch& a) {
     note_kernel(1, "fast_bwd_xfp_kernel");
-    const crossclr_plan* p = a.p;
-    const Geo& g = a.g;
-    dim3 grid(2 * p->bpad / 128, p->bwd_slices), block(256);
-    void* stream = a.stream;
-    const unsigned char* st = (const unsigned char*)a.stash;
-    const unsigned sb = (unsigned)a.stash_bytes;
-    const unsigned char* xfo = (const unsigned char*)a.cols;
-    const float *rz = a.rz, *wrz = a.wrz, *rz_cols = a.rz_cols, *wrz_cols = a.wrz_cols, *ks = a.ks, *kc = a.kc;
-    float* gbuf = a.gbuf;
-    const int accumulate = a.accumulate, tps2 = a.tps, mode = a.mode;
-    (void)grid; (void)block; (void)stream; (void)st; (void)sb; (void)xfo; (void)rz; (void)wrz; (void)rz_cols; (void)wrz_cols; (void)kc; (void)gbuf;
-    (void)accumulate; (void)tps2; (void)mode;
-#define CROSSCLR_LBP3(DK, SW, XP, TPRF, GRID)                                                                                                                                    \
-    do {                                                                                                                                                                         \
-        if (mode == 0) CROSSCLR_FAST_LAUNCH((fast_bwd_xfp_kernel<DK, SW, 0, XP, TPRF>), GRID, block, stream, xfo, st, sb, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps2, ks, kc);      \
-        else if (mode == 1) CROSSCLR_FAST_LAUNCH((fast_bwd_xfp_kernel<DK, SW, 1, XP, TPRF>), GRID, block, stream, xfo, st, sb, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps2, ks, kc); \
-        else CROSSCLR_FAST_LAUNCH((fast_bwd_xfp_kernel<DK, SW, 2, XP, TPRF>), GRID, block, stream, xfo, st, sb, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps2, ks, kc);                \
-    } while (0)
-#define CROSSCLR_LBP(DK, XP, TPRF, GRID) do { if (ks) CROSSCLR_LBP3(DK, true, XP, TPRF, GRID); else CROSSCLR_LBP3(DK, false, XP, TPRF, GRID); } while (0)
-    dim3 gridp2(2 * p->bpad / 128, p->bwd_slices, 2);
-    switch (p->Dpad) {
-        case 128: CROSSCLR_LBP(8, 1, 8, grid); break;
-        case 256: CROSSCLR_LBP(16, 1, 8, grid); break;
-        case 384: CROSSCLR_LBP(24, 1, 8, grid); break;
-        case 512: CROSSCLR_LBP(32, 1, 8, grid); break;
-        case 768: CROSSCLR_LBP(24, 2, 4, gridp2); break;      // two column parts of Dpad / 2 (blockIdx.z)
-        case 1024: CROSSCLR_LBP(32, 2, 4, gridp2); break;
-        default: return CROSSCLR_E_ARG;
-    }
-#undef CROSSCLR_LBP
-#undef CROSSCLR_LBP3
-    return CROSSCLR_OK;
+    return saved_shape(a.p->Dpad, [&a](auto s) {
+        using S = decltype(s);
+        return saved_launch(a.ks ? saved_xfp_kernel<S, true, 3>(a.kind.block) : saved_xfp_kernel<S, false, 3>(a.kind.block), a, S::XP);
+    });
 }
 #endif   // CROSSCLR_DEF_SAVED_XFP
 
@@ -999,185 +1043,74 @@ int launch_saved_xf1(const SavedLaunch& a);
 #else
 CROSSCLR_LEAF int launch_saved_xf1(const SavedLaunch& a) {
     note_kernel(1, "fast_bwd_dsl_kernel (fragment-major, one tile)");
-    const crossclr_plan* p = a.p;
-    const Geo& g = a.g;
-    dim3 grid(2 * p->bpad / 128, p->bwd_slices), block(256);
-    void* stream = a.stream;
-    const bf16_t* c = (const bf16_t*)a.cols;
-    const unsigned char* st = (const unsigned char*)a.stash;
-    const float *rz = a.rz, *wrz = a.wrz, *rz_cols = a.rz_cols, *wrz_cols = a.wrz_cols, *ks = a.ks, *kc = a.kc;
-    float* gbuf = a.gbuf;
-    const int accumulate = a.accumulate, tps = a.tps;
-    (void)grid; (void)block; (void)stream; (void)c; (void)st; (void)rz; (void)wrz; (void)rz_cols; (void)wrz_cols; (void)kc; (void)gbuf; (void)accumulate; (void)tps;
-#define CROSSCLR_LBX2(DK) do { dim3 grid2(2 * p->bpad / 128, p->bwd_slices, 2);                                                                  \
-                               if (ks) CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<DK, true, 0, 2, 4, true>), grid2, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc); \
-                               else CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<DK, false, 0, 2, 4, true>), grid2, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc); } while (0)
-#define CROSSCLR_LBX(DK) do { if (ks) CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<DK, true, 0, 1, 8, true>), grid, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc); \
-                              else CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<DK, false, 0, 1, 8, true>), grid, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc); } while (0)
-    switch (p->Dpad) {
-        case 128: CROSSCLR_LBX(8); break;
-        case 256: CROSSCLR_LBX(16); break;
-        case 384: CROSSCLR_LBX(24); break;
-        case 512: CROSSCLR_LBX(32); break;
-        case 768: CROSSCLR_LBX2(24); break;      // two column parts of Dpad / 2 (blockIdx.z), like the LDS-staged launch
-        case 1024: CROSSCLR_LBX2(32); break;
-        default: return CROSSCLR_E_ARG;
-    }
-#undef CROSSCLR_LBX
-#undef CROSSCLR_LBX2
-    return CROSSCLR_OK;
+    return saved_shape(a.p->Dpad, [&a](auto s) {
+        using S = decltype(s);
+        return saved_launch(a.ks ? saved_dsl_kernel<S, true, 1, true>(a.kind.block) : saved_dsl_kernel<S, false, 1, true>(a.kind.block), a, S::XP);
+    });
 }
 #endif   // CROSSCLR_DEF_SAVED_XF1
 
-// fast_bwd_dsl_kernel, column tiles staged through LDS: the local block (mode 0), rectangular blocks (1) and their transposes (2)
+// fast_bwd_dsl_kernel, column tiles staged through LDS: the local block, rectangular blocks and their transposes
 #ifndef CROSSCLR_DEF_SAVED_LDS
 int launch_saved_lds(const SavedLaunch& a);
 #else
 CROSSCLR_LEAF int launch_saved_lds(const SavedLaunch& a) {
     note_kernel(1, "fast_bwd_dsl_kernel (LDS-staged)");
-    const crossclr_plan* p = a.p;
-    const Geo& g = a.g;
-    dim3 grid(2 * p->bpad / 128, p->bwd_slices), block(256);
-    void* stream = a.stream;
-    const bf16_t* c = (const bf16_t*)a.cols;
-    const unsigned char* st = (const unsigned char*)a.stash;
-    const float *rz = a.rz, *wrz = a.wrz, *rz_cols = a.rz_cols, *wrz_cols = a.wrz_cols, *ks = a.ks, *kc = a.kc;
-    float* gbuf = a.gbuf;
-    const int accumulate = a.accumulate, tps = a.tps, mode = a.mode;
-    (void)grid; (void)block; (void)stream; (void)c; (void)st; (void)rz; (void)wrz; (void)rz_cols; (void)wrz_cols; (void)kc; (void)gbuf; (void)accumulate; (void)tps; (void)mode;
-#define CROSSCLR_LB3(DK, SW, XP, TPRF, GRID)                                                                                                   \
-    do {                                                                                                                                        \
-        if (mode == 0) CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<DK, SW, 0, XP, TPRF>), GRID, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc);      \
-        else if (mode == 1) CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<DK, SW, 1, XP, TPRF>), GRID, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc); \
-        else CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<DK, SW, 2, XP, TPRF>), GRID, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc);                \
-    } while (0)
-#define CROSSCLR_LB(DK, XP, TPRF, GRID) do { if (ks) CROSSCLR_LB3(DK, true, XP, TPRF, GRID); else CROSSCLR_LB3(DK, false, XP, TPRF, GRID); } while (0)
-    if (p->Dpad > 512) {   // two column parts of Dpad/2
-        dim3 grid2(2 * p->bpad / 128, p->bwd_slices, 2);
-        switch (p->Dpad) {
-            case 768: CROSSCLR_LB(24, 2, 4, grid2); break;
-            case 1024: CROSSCLR_LB(32, 2, 4, grid2); break;
-            default: return CROSSCLR_E_ARG;
-        }
-        return CROSSCLR_OK;
-    }
-    switch (p->Dpad) {
-        case 128: CROSSCLR_LB(8, 1, 8, grid); break;
-        case 256: CROSSCLR_LB(16, 1, 8, grid); break;
-        case 384: CROSSCLR_LB(24, 1, 8, grid); break;
-        case 512: CROSSCLR_LB(32, 1, 8, grid); break;
-        default: return CROSSCLR_E_ARG;
-    }
-#undef CROSSCLR_LB
-#undef CROSSCLR_LB3
-    return CROSSCLR_OK;
+    return saved_shape(a.p->Dpad, [&a](auto s) {
+        using S = decltype(s);
+        return saved_launch(a.ks ? saved_dsl_kernel<S, true, 3, false>(a.kind.block) : saved_dsl_kernel<S, false, 3, false>(a.kind.block), a, S::XP);
+    });
 }
 #endif   // CROSSCLR_DEF_SAVED_LDS
 
-// fast_bwd_dsl_kernel for wide bf16 plans (Dpad > 1024: 3 ... 8 column parts, blockIdx.z): the local symmetric block from the records the
-// generic forward saved (fwd_sums_kernel<bf16_t, ..., ST, SYM>)
+// fast_bwd_dsl_kernel for wide bf16 plans (Dpad > 1024: 3 ... 16 column parts, blockIdx.z): the local symmetric block from the records the
+// generic forward saved (fwd_sums_kernel<bf16_t, ..., ST, SYM>), and a rectangular block against other ranks' columns
+// (crossclr_backward_rect_saved)
 #ifndef CROSSCLR_DEF_SAVED_WIDE
 int launch_saved_wide(const SavedLaunch& a);
 int launch_saved_wide_xfp(const SavedLaunch& a);
 #else
 CROSSCLR_LEAF int launch_saved_wide(const SavedLaunch& a) {
     note_kernel(1, "fast_bwd_dsl_kernel (wide, column parts)");
-    const crossclr_plan* p = a.p;
-    const Geo& g = a.g;
-    dim3 block(256);
-    void* stream = a.stream;
-    const bf16_t* c = (const bf16_t*)a.cols;
-    const unsigned char* st = (const unsigned char*)a.stash;
-    const float *rz = a.rz, *wrz = a.wrz, *rz_cols = a.rz_cols, *wrz_cols = a.wrz_cols, *ks = a.ks, *kc = a.kc;
-    float* gbuf = a.gbuf;
-    const int accumulate = a.accumulate, tps = a.tps;
-    (void)block; (void)stream; (void)c; (void)st; (void)rz; (void)wrz; (void)rz_cols; (void)wrz_cols; (void)kc; (void)gbuf; (void)accumulate; (void)tps;
-    const int mode = a.mode;
-    if (mode != 0 && mode != 1) return CROSSCLR_E_ARG;       // (1: a rectangular block against other ranks' columns, crossclr_backward_rect_saved)
-#define CROSSCLR_LBW2(DK, XP, SW) do { if (mode == 0) CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<DK, SW, 0, XP, 4>), gridw, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc); \
-                                       else CROSSCLR_FAST_LAUNCH((fast_bwd_dsl_kernel<DK, SW, 1, XP, 4>), gridw, block, stream, c, st, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps, ks, kc); } while (0)
-#define CROSSCLR_LBW(DK, XP) do { dim3 gridw(2 * p->bpad / 128, p->bwd_slices, XP);                                                            \
-                                  if (ks) CROSSCLR_LBW2(DK, XP, true); else CROSSCLR_LBW2(DK, XP, false); } while (0)
-    switch (p->Dpad) {
-        case 1152: CROSSCLR_LBW(24, 3); break;
-        case 1536: CROSSCLR_LBW(32, 3); break;
-        case 2048: CROSSCLR_LBW(32, 4); break;
-        case 2560: CROSSCLR_LBW(32, 5); break;
-        case 3072: CROSSCLR_LBW(32, 6); break;
-        case 4096: CROSSCLR_LBW(32, 8); break;
-        case 5120: CROSSCLR_LBW(32, 10); break;
-        case 6144: CROSSCLR_LBW(32, 12); break;
-        case 8192: CROSSCLR_LBW(32, 16); break;
-        default: return CROSSCLR_E_ARG;
-    }
-#undef CROSSCLR_LBW
-#undef CROSSCLR_LBW2
-    return CROSSCLR_OK;
+    return saved_shape_wide(a.p->Dpad, [&a](auto s) {
+        using S = decltype(s);
+        return saved_launch(a.ks ? saved_dsl_kernel<S, true, 2, false>(a.kind.block) : saved_dsl_kernel<S, false, 2, false>(a.kind.block), a, S::XP);
+    });
 }
-// the same on the fragment-major operand with the pair kernel (crossclr_kernels_dslp.h): what the module takes from 4096 padded rows on
+// the local block on the fragment-major operand with the pair kernel (crossclr_kernels_dslp.h): what the module takes from 4096 padded rows on
 CROSSCLR_LEAF int launch_saved_wide_xfp(const SavedLaunch& a) {
     note_kernel(1, "fast_bwd_xfp_kernel (wide, column parts)");
-    const crossclr_plan* p = a.p;
-    const Geo& g = a.g;
-    dim3 block(256);
-    void* stream = a.stream;
-    const unsigned char* st = (const unsigned char*)a.stash;
-    const unsigned sb = (unsigned)a.stash_bytes;
-    const unsigned char* xfo = (const unsigned char*)a.cols;
-    const float *rz = a.rz, *wrz = a.wrz, *rz_cols = a.rz_cols, *wrz_cols = a.wrz_cols, *ks = a.ks, *kc = a.kc;
-    float* gbuf = a.gbuf;
-    const int accumulate = a.accumulate, tps2 = a.tps;
-    (void)block; (void)stream; (void)st; (void)sb; (void)xfo; (void)rz; (void)wrz; (void)rz_cols; (void)wrz_cols; (void)kc; (void)gbuf; (void)accumulate; (void)tps2;
-    if (a.mode != 0) return CROSSCLR_E_ARG;
-#define CROSSCLR_LBWP(DK, XP) do { dim3 gridw(2 * p->bpad / 128, p->bwd_slices, XP);                                                            \
-                                   if (ks) CROSSCLR_FAST_LAUNCH((fast_bwd_xfp_kernel<DK, true, 0, XP, 4>), gridw, block, stream, xfo, st, sb, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps2, ks, kc); \
-                                   else CROSSCLR_FAST_LAUNCH((fast_bwd_xfp_kernel<DK, false, 0, XP, 4>), gridw, block, stream, xfo, st, sb, g, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, tps2, ks, kc); } while (0)
-    switch (p->Dpad) {
-        case 1152: CROSSCLR_LBWP(24, 3); break;
-        case 1536: CROSSCLR_LBWP(32, 3); break;
-        case 2048: CROSSCLR_LBWP(32, 4); break;
-        case 2560: CROSSCLR_LBWP(32, 5); break;
-        case 3072: CROSSCLR_LBWP(32, 6); break;
-        case 4096: CROSSCLR_LBWP(32, 8); break;
-        case 5120: CROSSCLR_LBWP(32, 10); break;
-        case 6144: CROSSCLR_LBWP(32, 12); break;
-        case 8192: CROSSCLR_LBWP(32, 16); break;
-        default: return CROSSCLR_E_ARG;
-    }
-#undef CROSSCLR_LBWP
-    return CROSSCLR_OK;
+    return saved_shape_wide(a.p->Dpad, [&a](auto s) {
+        using S = decltype(s);
+        return saved_launch(a.ks ? saved_xfp_kernel<S, true, 1>(a.kind.block) : saved_xfp_kernel<S, false, 1>(a.kind.block), a, S::XP);
+    });
 }
 #endif   // CROSSCLR_DEF_SAVED_WIDE
 
-// mode 0 / 1 / 2: the LDS-staged kernel on the row-major operand -- the local symmetric block, a rectangular block, the transpose of one
-// rectangular block.  mode 3: mode 0 on the fragment-major operand, one tile per barrier interval.  mode 4 / 5 / 6: modes 0 / 1 / 2 on the
-// fragment-major operand with the pair kernel (crossclr_kernels_dslp.h; stash below 4 GiB: 32-bit scalar offsets, even slices).
-static inline int fast_backward_saved(const crossclr_plan* p, const Geo& g, const void* cols, const void* stash, const float* rz,
+// kind.block over kind.operand (see SavedBlock / SavedOperand above).  Every slice holds an EVEN number of tiles (the pair kernel needs it; the
+// other kernels take the same cut so that all of them produce the same bits slice by slice).
+static inline int fast_backward_saved(SavedKind kind, const crossclr_plan* p, const Geo& g, const void* cols, const void* stash, const float* rz,
                                       const float* wrz, const float* rz_cols, const float* wrz_cols, float* gbuf, int accumulate,
-                                      const float* ks, const float* kc, int mode, void* stream) {
-    const bool xfp = mode >= 4;
-    const bool xf = mode == 3 || xfp;
-    if (xfp) mode -= 4;
-    if (mode == 3) mode = 0;
-    const bool rect = mode == 1;
+                                      const float* ks, const float* kc, void* stream) {
+    const bool rect = kind.block == SavedBlock::Rect;
     const bool skipping = rect && g.col_wrap == 0 && g.skip_rank >= g.col_rank0 && g.skip_rank < g.col_rank0 + g.col_ranks;
     const int per_rank = 2 * p->bpad / 32;
     const int ntiles = (rect ? g.col_ranks - (skipping ? 1 : 0) : 1) * per_rank;
     if (ntiles <= 0) return CROSSCLR_OK;
-    int tps = (ntiles + p->bwd_slices - 1) / p->bwd_slices;
-    // every slice holds an EVEN number of tiles (the pair kernel needs it; the other kernels take the same cut so that all of them
-    // produce the same bits slice by slice)
-    tps = (tps + 1) & ~1;
-    SavedLaunch a = {p, g, cols, stash, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, ks, kc, mode, tps, stream, 0};
-    if (xfp) {
-        // the saved exponentials are addressed with 32-bit scalar offsets: local triangle / [row group][usable tile] / [row group][segments x tile]
-        a.stash_bytes = mode == 0 ? p->stash_bytes
-                                  : (size_t)per_rank * (size_t)(mode == 1 ? ntiles : g.col_ranks * per_rank) * 2048;
-        if (a.stash_bytes >= ((size_t)1 << 32)) return CROSSCLR_E_ARG;
-        return p->Dpad > 1024 ? launch_saved_wide_xfp(a) : launch_saved_xfp(a);
+    const int tps = ((ntiles + p->bwd_slices - 1) / p->bwd_slices + 1) & ~1;
+    SavedLaunch a = {p, g, cols, stash, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, ks, kc, kind, tps, stream, 0};
+    const bool wide = p->Dpad > 1024;      // (wide plans: the pair kernel or the LDS-staged one)
+    switch (kind.operand) {
+        case SavedOperand::RowMajor: return wide ? launch_saved_wide(a) : launch_saved_lds(a);
+        case SavedOperand::FragmentOne: return wide ? CROSSCLR_E_ARG : launch_saved_xf1(a);
+        case SavedOperand::FragmentPair:
+            // the saved exponentials are addressed with 32-bit scalar offsets: local triangle / [row group][usable tile] / [row group][segments x tile]
+            a.stash_bytes = kind.block == SavedBlock::Local ? p->stash_bytes
+                                                            : (size_t)per_rank * (size_t)(rect ? ntiles : g.col_ranks * per_rank) * 2048;
+            if (a.stash_bytes >= ((size_t)1 << 32)) return CROSSCLR_E_ARG;
+            return wide ? launch_saved_wide_xfp(a) : launch_saved_xfp(a);
     }
-    if (p->Dpad > 1024) return xf ? CROSSCLR_E_ARG : launch_saved_wide(a);     // (wide plans: the pair kernel or the LDS-staged one)
-    return xf ? launch_saved_xf1(a) : launch_saved_lds(a);
+    return CROSSCLR_E_ARG;
 }
 // which backward the fast path uses: 16-row wavefronts (rows per block 128 at Dpad <= 512, 64 above) or the
 // 32-row kernel (Dpad <= 512 only)

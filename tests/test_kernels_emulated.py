@@ -596,3 +596,110 @@ def test_two_pass_regime_bf16_plans_save_their_exponentials(B, D, weighted, monk
         ref = orc.streaming_loss_and_grads(v, t, 0.004, 0.8)
         assert abs(ls - float(ref["loss"])) <= 2e-2 * max(1.0, abs(float(ref["loss"])))
         assert (gvs.double() - ref["grad_v"]).abs().max().item() <= 3e-2 * scale
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+def test_pair_scheme_saved_blocks_through_the_c_abi(weighted):
+    """The pair-scheme walk of tests/test_gpu_parity.py (test_remote_blocks_with_saved_exponentials_equal_single_device, partner gradients)
+    at the smallest shape that reaches it -- three ranks of 64 rows, D = 128, bf16 -- with every rank played through the C-ABI of the
+    emulated library: crossclr_backward_rect_saved_xfp must reproduce crossclr_backward_rect_saved BIT FOR BIT, crossclr_backward_rect_saved_t_xfp
+    likewise crossclr_backward_rect_saved_t, and loss and gradients assembled from the saved blocks equal the single-device run."""
+    from crossclr_amd import loss as L
+    lib, p = nat.library(), L._ptr
+    world, b, D = 3, 64, 128
+    B = world * b
+    v, t = orc.make_inputs("randn", B, D, 71)
+    g = torch.Generator().manual_seed(3)
+    kv = (torch.rand(B, generator=g) > 0.2).float()
+    kt = (torch.rand(B, generator=g) > 0.2).float()
+    ov = 0.5 + torch.rand(B, generator=g)
+    ot = 0.5 + torch.rand(B, generator=g)
+    plans = [nat.make_plan(b, D, world, r, nat.MODE_BF16) for r in range(world)]
+    pl = plans[0]
+    assert pl.fast_path == 1 and pl.stash_bytes > 0 and pl.xf_bytes == pl.operand_bytes
+    n2 = 2 * pl.bpad
+    xall = torch.empty(world * pl.operand_bytes, dtype=torch.uint8)
+    inv = [torch.empty(n2) for _ in range(world)]
+    diag = [torch.empty(pl.bpad) for _ in range(world)]
+    kall, lwall = torch.zeros(world, 2, pl.bpad), torch.zeros(world, 2, pl.bpad)
+    kall[:, 0, :b], kall[:, 1, :b] = kv.view(world, b), kt.view(world, b)
+    lwall[:, 0, :b], lwall[:, 1, :b] = ov.view(world, b), ot.view(world, b)
+
+    def sw(r, cols_all, lw):
+        if not weighted:
+            return None
+        return ctypes.pointer(nat.SampleWeights(kall[r].data_ptr(), kall.data_ptr() if cols_all else kall[r].data_ptr(),
+                                                lwall[r].data_ptr() if lw else 0))
+    for r in range(world):
+        xr = xall[r * pl.operand_bytes:(r + 1) * pl.operand_bytes]
+        nat.check(lib.crossclr_normalize(ctypes.byref(plans[r]), p(v[r * b:]), p(t[r * b:]), v.stride(0), t.stride(0), nat.IN_F32,
+                                         p(xr), p(inv[r]), p(diag[r]), None))
+    K = (world - 1) // 2
+    assert K == 1
+    parts = [torch.empty(pl.fwd_ws_floats) for _ in range(world)]
+    colsums = [torch.zeros(K, n2) for _ in range(world)]
+    stashes, blocks = [], []
+    for r in range(world):
+        pp = ctypes.byref(plans[r])
+        xr = xall[r * pl.operand_bytes:(r + 1) * pl.operand_bytes]
+        st_loc = torch.empty(pl.stash_bytes, dtype=torch.uint8)
+        nat.check(lib.crossclr_forward_save(pp, p(xr), 0.03, 0.8, sw(r, False, False), p(parts[r]), 0, p(st_loc), None))
+        st = torch.empty(lib.crossclr_rect_stash_bytes(pp, K), dtype=torch.uint8)
+        nat.check(lib.crossclr_forward_rect_save(pp, p(xr), p(xall), (r + 1) % world, K, 1, 0.03, 0.8, sw(r, True, False), p(parts[r]),
+                                                 pl.fwd_slots, p(colsums[r]), p(st), None))
+        nat.check(lib.crossclr_forward_add(pp, p(parts[r]), 2 * pl.fwd_slots, None, None))
+        stashes.append(st_loc)
+        blocks.append(((r + 1) % world, K, st))
+    rz, wrz = torch.empty(world, n2), torch.empty(world, n2)
+    total = torch.zeros(1, dtype=torch.float64)
+    for r in range(world):
+        pp = ctypes.byref(plans[r])
+        received = colsums[(r - 1) % world][0].clone()       # rank r-1 evaluated the pair and computed this rank's sums as its colsum[0]
+        nat.check(lib.crossclr_forward_add(pp, p(parts[r]), 3 * pl.fwd_slots, p(received), None))
+        logz = torch.empty(n2)
+        ls = torch.empty(pl.loss_ws_doubles, dtype=torch.float64)
+        nat.check(lib.crossclr_forward_finish_w(pp, p(parts[r]), 4 * pl.fwd_slots, p(diag[r]), 0.03, 0.8, sw(r, False, True), p(logz),
+                                                p(rz[r]), p(wrz[r]), p(ls), None))
+        total += ls[:1]
+    lossN = (total / (2.0 * B)).item()
+    gv, gt = torch.empty_like(v), torch.empty_like(t)
+    go = torch.ones(1, dtype=torch.float64)
+    xfall = torch.empty(world * pl.operand_bytes, dtype=torch.uint8)
+    nat.check(lib.crossclr_pack_xf_from_packed(ctypes.byref(pl), p(xall), world, p(xfall), None))
+    nel = n2 * pl.Dpad
+    for r in range(world):
+        pp = ctypes.byref(plans[r])
+        xr = xall[r * pl.operand_bytes:(r + 1) * pl.operand_bytes]
+        gbuf = torch.empty(pl.gbuf_bytes // 4)
+        nat.check(lib.crossclr_backward_saved(pp, p(xr), p(stashes[r]), 0.03, 0.8, p(rz[r]), p(wrz[r]), sw(r, False, False), p(gbuf), 0, None))
+        first, n, st = blocks[r]
+        twin = gbuf.clone()
+        nat.check(lib.crossclr_backward_rect_saved(pp, p(xall), p(st), first, n, 0.03, 0.8, p(rz[r]), p(wrz[r]), p(rz), p(wrz),
+                                                   sw(r, True, False), p(gbuf), 1, None))
+        nat.check(lib.crossclr_backward_rect_saved_xfp(pp, p(xfall), p(st), first, n, 0.03, 0.8, p(rz[r]), p(wrz[r]), p(rz), p(wrz),
+                                                       sw(r, True, False), p(twin), 1, None))
+        assert torch.equal(twin, gbuf), r
+        # partner gradients: rank src = r-1 evaluated block (src, r) and forms its transposed contribution to r's buffer
+        src = (r - 1) % world
+        xs = xall[src * pl.operand_bytes:(src + 1) * pl.operand_bytes]
+        xfs = xfall[src * pl.operand_bytes:(src + 1) * pl.operand_bytes]
+        first, n, st = blocks[src]
+        tmp = torch.empty(pl.gbuf_bytes // 4)
+        tmp2 = torch.full_like(tmp, float("nan"))
+        nat.check(lib.crossclr_backward_rect_saved_t(ctypes.byref(plans[src]), p(xs), p(st), first, n, 0, 0.03, 0.8, p(rz[src]),
+                                                     p(wrz[src]), p(rz), p(wrz), sw(src, True, False), p(tmp), None))
+        nat.check(lib.crossclr_backward_rect_saved_t_xfp(ctypes.byref(plans[src]), p(xfs), p(st), first, n, 0, 0.03, 0.8, p(rz[src]),
+                                                         p(wrz[src]), p(rz), p(wrz), sw(src, True, False), p(tmp2), None))
+        assert torch.equal(tmp2, tmp), (r, src)
+        gbuf[:nel] += tmp.view(-1, nel).sum(0)
+        nat.check(lib.crossclr_backward_finish_w(pp, p(gbuf), p(v[r * b:]), p(t[r * b:]), v.stride(0), t.stride(0), nat.IN_F32,
+                                                 p(inv[r]), 0.03, sw(r, False, True), p(go), p(gv[r * b:]), p(gt[r * b:]),
+                                                 gv.stride(0), gt.stride(0), None))
+    vg, tg = v.clone().requires_grad_(True), t.clone().requires_grad_(True)
+    loss1 = crossclr_amd.crossclr_loss(vg, tg, 0.03, 0.8, compute_mode="bf16", negative_scale=(kv, kt) if weighted else None,
+                                       loss_weight=(ov, ot) if weighted else None)
+    loss1.backward()
+    assert abs(lossN - loss1.item()) <= 2e-6 * max(1.0, abs(loss1.item()))
+    scale = vg.grad.abs().max().item()
+    assert (gv - vg.grad).abs().max().item() <= 3e-3 * scale      # bf16 weights rounded in different tile groupings
+    assert (gt - tg.grad).abs().max().item() <= 3e-3 * scale
