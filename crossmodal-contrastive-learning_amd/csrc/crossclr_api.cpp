@@ -6,11 +6,9 @@
 #include "crossclr_kernels_generic.h"
 #include "crossclr_kernels_hvp.h"
 #include "crossclr_kernels_topk.h"
-#ifndef CROSSCLR_NO_FAST
 #include "crossclr_kernels_fast.h"
 #include "crossclr_kernels_project.h"
 #include "crossclr_kernels_saved32.h"
-#endif
 
 #include <math.h>
 #include <stdarg.h>
@@ -82,6 +80,20 @@ static int refuse_x3(const char* what) {
 // label of a generic launch (crossclr_last_kernel): the split-operand instantiations carry <x3_t>
 template <typename T> static const char* glabel(const char* plain, const char* x3) { return std::is_same<T, x3_t>::value ? x3 : plain; }
 static const float* const kNoF = nullptr;     // (kernel arguments a launch does not use)
+// the packed operand's element type from plan->mode -- f(type_tag<float>()), f(type_tag<x3_t>()) or f(type_tag<bf16_t>()); SPLIT = false:
+// entry points without split-operand kernels (they refuse CROSSCLR_MODE_BF16X3 before they get here): float or bf16_t only
+template <typename T> struct type_tag { using type = T; };
+template <bool SPLIT = true, class F> static int with_plan_type(const crossclr_plan* plan, F f) {
+    if (plan->mode == CROSSCLR_MODE_FP32) return f(type_tag<float>());
+    if constexpr (SPLIT) if (is_x3(plan)) return f(type_tag<x3_t>());
+    return f(type_tag<bf16_t>());
+}
+// D columns per thread block: the first of DCS... that divides Dpad (the last one, 64, always does) -- f(std::integral_constant<int, DC>())
+template <int DC, int... REST, class F> static void with_d_chunk(int Dpad, F f) {
+    if constexpr (sizeof...(REST) == 0) f(std::integral_constant<int, DC>());
+    else if (Dpad % DC == 0) f(std::integral_constant<int, DC>());
+    else with_d_chunk<REST...>(Dpad, f);
+}
 
 // tuning knobs from the environment, read ONCE per process (not per call: crossclr_make_plan sits on the step's host path)
 struct EnvKnobs {
@@ -110,9 +122,6 @@ static const EnvKnobs& env_knobs() {
     return k;
 #endif
 }
-static int forward_generic(const crossclr_plan* plan, const Geo& g, const void* rows, const void* cols, float* out,
-                           const float* kcols, const float* shift, int mode, void* stream, float* stash = nullptr,
-                           const float* shift_cols = nullptr);
 
 // forward workspace ("part") layout, in floats:
 //   [4 launch groups][fwd_slots][2*bpad] | colpart (symmetric launch) [<= 2*bpad/128 row blocks][2*bpad]
@@ -149,6 +158,18 @@ static int device_zero_header(int* where, void* stream) {  // kind 0 = dense slo
     return CROSSCLR_OK;
 #endif
 }
+// one launch group of the forward workspace: its partial sums, its header, and the two column-partial regions (shared by the groups)
+struct FwdSlot { float* out; int* header; float* colpart; float* paircol; };
+static FwdSlot fwd_group(const crossclr_plan* plan, float* part, int group) {
+    return {part + (size_t)group * plan->fwd_slots * 2 * plan->bpad, reinterpret_cast<int*>(part + ws_flag_off(plan)) + 4 * group,
+            part + ws_colpart_off(plan), part + ws_paircol_off(plan)};
+}
+static int fwd_slot(const crossclr_plan* plan, float* part, int slot0, FwdSlot* s) {
+    if (plan->fwd_slots <= 0 || slot0 < 0 || slot0 % plan->fwd_slots != 0 || slot0 / plan->fwd_slots >= kLaunchGroups)
+        return fail(CROSSCLR_E_ARG, "slot0 must be L * plan->fwd_slots, L = 0..%d", kLaunchGroups - 1);
+    *s = fwd_group(plan, part, slot0 / plan->fwd_slots);
+    return CROSSCLR_OK;
+}
 
 extern "C" int crossclr_make_plan(int b, int D, int world, int rank, int mode, crossclr_plan* plan) {
     if (!plan) return fail(CROSSCLR_E_ARG, "plan is NULL");
@@ -170,33 +191,27 @@ extern "C" int crossclr_make_plan(int b, int D, int world, int rank, int mode, c
     plan->bpad = round_up(b, kRowPad);
     plan->fast_path = 0;
     int dpad = round_up(D, 64);
-#ifndef CROSSCLR_NO_FAST
     const EnvKnobs& env = env_knobs();
     if (mode == CROSSCLR_MODE_BF16 && !env.disable_fast) {  // env knob: A/B against the generic path
         int fp = fast_dpad(D);
         if (fp > 0) { dpad = fp; plan->fast_path = 1; }
     }
-#endif
     if (!plan->fast_path && dpad > 256) dpad = round_up(D, 256);  // generic backward slices D by 256
     // wide bf16 plans (1024 < D <= 8192): generic forward, but its exponentials are saved for the D-slice backward, which runs as 3 ... 16
     // column parts of 384 / 512 columns -- the operand is padded to parts x columns
     bool wide = false;
-#ifndef CROSSCLR_NO_FAST
     if (mode == CROSSCLR_MODE_BF16 && !plan->fast_path && !env.disable_fast && !env.disable_save && !env.disable_symmetric && wide_bf16_dpad(D) > 0) {
         dpad = wide_bf16_dpad(D);
         wide = true;
     }
-#endif
     plan->Dpad = dpad;
     // backward kernel: 0 generic tiled, 1 register-resident 32-row waves (Dpad <= 512), 2 16-row waves (Dpad <= 1024)
     plan->fast_bwd = 0;
-#ifndef CROSSCLR_NO_FAST
     if (mode == CROSSCLR_MODE_BF16 && !env.disable_fast) {
         if (plan->fast_path) plan->fast_bwd = dpad <= 512 ? CROSSCLR_DEFAULT_BWD_KERNEL : 2;
         if (env.bwd_kernel == 16 && plan->fast_path) plan->fast_bwd = 2;              // tuning knob: 16 or 32
         if (env.bwd_kernel == 32 && plan->fast_path && dpad <= 512) plan->fast_bwd = 1;
     }
-#endif
     // forward partial-sum slots.  generic kernels: (row block x column split) grid, enough work items to
     // fill 256 CUs a few times over.  fast path: persistent blocks over a flat work list (see FwdWork);
     // a row block's slots = the thread blocks whose range touches it.
@@ -206,7 +221,6 @@ extern "C" int crossclr_make_plan(int b, int D, int world, int rank, int mode, c
     if (nsplit > col_tiles) nsplit = col_tiles;
     if (nsplit < 1) nsplit = 1;
     plan->fwd_blocks = 0;
-#ifndef CROSSCLR_NO_FAST
     if (plan->fast_path) {
         plan->fwd_blocks = 256;  // one persistent block per MI355X CU (LDS-limited to one block per CU)
         if (env.fwd_blocks >= 1 && env.fwd_blocks <= 4096) plan->fwd_blocks = env.fwd_blocks;   // tuning knob
@@ -223,7 +237,6 @@ extern "C" int crossclr_make_plan(int b, int D, int world, int rank, int mode, c
         }
         nsplit = slots;
     }
-#endif
     plan->fwd_slots = nsplit;
     plan->fwd_ws_floats = 0;  // set below
     // backward column slices: each slice walks its share of the column tiles and writes its own gradient
@@ -231,9 +244,7 @@ extern "C" int crossclr_make_plan(int b, int D, int world, int rank, int mode, c
     {
         const int tile = plan->fast_bwd ? 32 : 64;
         int row_blk = 64;
-#ifndef CROSSCLR_NO_FAST
         if (plan->fast_bwd) row_blk = fast_bwd_rows_per_block(plan->Dpad, plan->fast_bwd == 2);
-#endif
         int dsl = 1;
         if (!plan->fast_bwd) dsl = plan->Dpad % 256 == 0 ? plan->Dpad / 256 : (plan->Dpad % 128 == 0 ? plan->Dpad / 128 : plan->Dpad / 64);
         const int blocks = (2 * plan->bpad / row_blk) * dsl;
@@ -265,7 +276,6 @@ extern "C" int crossclr_make_plan(int b, int D, int world, int rank, int mode, c
     plan->operand_bytes = (size_t)2 * plan->bpad * plan->Dpad * esz;
     plan->gbuf_bytes = (size_t)plan->bwd_slices * 2 * plan->bpad * plan->Dpad * 4;
     plan->stash_bytes = 0;
-#ifndef CROSSCLR_NO_FAST
     if (plan->fast_path && plan->fast_bwd && !env.disable_save) plan->stash_bytes = fast_stash_bytes(plan->bpad, plan->Dpad);
     if (wide) plan->stash_bytes = wide_stash_bytes(plan->bpad);
     if (wide && plan->stash_bytes && !env.disable_xf && plan->operand_bytes < ((size_t)1 << 32)) plan->xf_bytes = plan->operand_bytes;
@@ -276,9 +286,6 @@ extern "C" int crossclr_make_plan(int b, int D, int world, int rank, int mode, c
     }
     // the fragment-major copy of the bf16 operand (crossclr_normalize_xf -> crossclr_backward_saved_xf): local block, Dpad <= 1024
     if (plan->fast_path && plan->fast_bwd && plan->stash_bytes && plan->Dpad <= 1024 && !env.disable_xf) plan->xf_bytes = plan->operand_bytes;
-#else
-    plan->xf_bytes = 0;
-#endif
     return CROSSCLR_OK;
 }
 
@@ -323,16 +330,12 @@ static int normalize_t(const crossclr_plan* p, const void* v, const void* t, lon
     Geo g; memset(&g, 0, sizeof(g));
     g.b = p->b; g.bpad = p->bpad; g.D = p->D; g.Dpad = p->Dpad;
     dim3 grid((p->bpad + 3) / 4), block(256);
-    if (p->mode == CROSSCLR_MODE_FP32)
-        LAUNCH((normalize_kernel<TIN, float, NORM>), grid, block, stream, (const TIN*)v, (const TIN*)t, ldv, ldt, g,
-               (float*)xhat, inv_norm, diag, zero_word);
-    else if (is_x3(p))
-        LAUNCH((normalize_kernel<TIN, x3_t, NORM>), grid, block, stream, (const TIN*)v, (const TIN*)t, ldv, ldt, g,
-               (x3_t*)xhat, inv_norm, diag, zero_word);
-    else
-        LAUNCH((normalize_kernel<TIN, bf16_t, NORM>), grid, block, stream, (const TIN*)v, (const TIN*)t, ldv, ldt, g,
-               (bf16_t*)xhat, inv_norm, diag, zero_word);
-    return launch_status("normalize_kernel");
+    return with_plan_type(p, [&](auto t_out) {
+        using T = typename decltype(t_out)::type;
+        LAUNCH((normalize_kernel<TIN, T, NORM>), grid, block, stream, (const TIN*)v, (const TIN*)t, ldv, ldt, g, (T*)xhat, inv_norm, diag,
+               zero_word);
+        return launch_status("normalize_kernel");
+    });
 }
 template <bool NORM>
 static int normalize_any(const crossclr_plan* plan, const void* video, const void* text, long ld_video, long ld_text, int in_dtype,
@@ -348,7 +351,6 @@ static int normalize_any(const crossclr_plan* plan, const void* video, const voi
     return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
 }
 
-#ifndef CROSSCLR_NO_FAST
 template <typename TIN, bool NORM>
 static int normalize_xf_t(const crossclr_plan* p, const void* v, const void* t, long ldv, long ldt, void* xhat, void* xf,
                           float* inv_norm, float* diag, void* stream, int* zero_word) {
@@ -362,15 +364,11 @@ static int normalize_xf_t(const crossclr_plan* p, const void* v, const void* t, 
                (bf16_t*)xhat, (unsigned char*)xf, inv_norm, diag, zero_word);
     return launch_status("normalize_xf_kernel");
 }
-#endif
 template <bool NORM>
 static int normalize_xf_any(const crossclr_plan* plan, const void* video, const void* text, long ld_video, long ld_text, int in_dtype,
                             void* xhat, void* xf, float* inv_norm, float* diag_cos, void* stream, int* zero_word = nullptr) {
     if (!plan || !video || !text || !xhat || !xf || !inv_norm || !diag_cos) return fail(CROSSCLR_E_ARG, "NULL argument");
     if (ld_video < plan->D || ld_text < plan->D) return fail(CROSSCLR_E_ARG, "row stride smaller than D");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "the fragment-major operand needs the register-resident path");
-#else
     if (!plan->xf_bytes) return fail(CROSSCLR_E_ARG, "this plan has no fragment-major operand (xf_bytes == 0): use crossclr_normalize / crossclr_pack");
     if (plan->Dpad > 1024) {   // wide plans: the row kernel, then the packed rows re-laid fragment-major (1024 columns of a 32-row tile per block)
         if (int rc = normalize_any<NORM>(plan, video, text, ld_video, ld_text, in_dtype, xhat, inv_norm, diag_cos, stream, zero_word)) return rc;
@@ -383,7 +381,6 @@ static int normalize_xf_any(const crossclr_plan* plan, const void* video, const 
         case CROSSCLR_IN_BF16: return normalize_xf_t<in_bf16, NORM>(plan, video, text, ld_video, ld_text, xhat, xf, inv_norm, diag_cos, stream, zero_word);
     }
     return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
-#endif
 }
 extern "C" int crossclr_normalize_xf(const crossclr_plan* plan, const void* video, const void* text, long ld_video, long ld_text,
                                      int in_dtype, void* xhat, void* xhat_xf, float* inv_norm, float* diag_cos, void* stream) {
@@ -407,7 +404,6 @@ extern "C" int crossclr_normalize(const crossclr_plan* plan, const void* video, 
 
 // ------------------------------------------------------------------------------------------------
 // producer-side fusion (crossclr_kernels_project.h)
-#ifndef CROSSCLR_NO_FAST
 template <typename TIN, bool WF>
 static int project_pack_t(const crossclr_plan* p, const void* xv, const void* xt, long ldv, long ldt, int Din_v, int Din_t, const void* wv,
                           const void* wt, int ldw_v, int ldw_t, const float* bv, const float* bt, void* xhat, float* inv_norm, float* diag,
@@ -433,16 +429,12 @@ static int project_pack_t(const crossclr_plan* p, const void* xv, const void* xt
 #undef CROSSCLR_LPPX
     return launch_status("project_pack_kernel");
 }
-#endif
 
 template <bool WF>
 static int project_pack_any(const crossclr_plan* plan, const void* x_video, const void* x_text, long ld_video, long ld_text,
                             int Din_video, int Din_text, int in_dtype, const void* w_video, const void* w_text, int ldw_video,
                             int ldw_text, const float* bias_video, const float* bias_text, void* xhat, float* inv_norm, float* diag_cos, void* stream) {
     if (!plan || !x_video || !x_text || !w_video || !w_text || !xhat || !inv_norm || !diag_cos) return fail(CROSSCLR_E_ARG, "NULL argument");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "crossclr_project_pack needs the register-resident path");
-#else
     if (plan->mode != CROSSCLR_MODE_BF16 || !plan->fast_path || plan->Dpad > 1024)
         return fail(CROSSCLR_E_ARG, "crossclr_project_pack: bf16 plans with D <= 1024 only");
     if (Din_video < 1 || Din_text < 1 || ld_video < Din_video || ld_text < Din_text) return fail(CROSSCLR_E_ARG, "row stride smaller than Din");
@@ -455,7 +447,6 @@ static int project_pack_any(const crossclr_plan* plan, const void* x_video, cons
         case CROSSCLR_IN_BF16: return project_pack_t<in_bf16, WF>(plan, x_video, x_text, ld_video, ld_text, Din_video, Din_text, w_video, w_text, ldw_video, ldw_text, bias_video, bias_text, xhat, inv_norm, diag_cos, stream);
     }
     return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
-#endif
 }
 extern "C" int crossclr_project_pack(const crossclr_plan* plan, const void* x_video, const void* x_text, long ld_video, long ld_text,
                                      int Din_video, int Din_text, int in_dtype, const void* w_video, const void* w_text, int ldw_video,
@@ -520,9 +511,6 @@ extern "C" int crossclr_project_backward_prep(const crossclr_plan* plan, const f
                                               long ld_gt, const void* xhat, const float* inv_norm, float* gy_video, float* gy_text,
                                               long ld_out, void* stream) {
     if (!plan || !g_video || !g_text || !xhat || !inv_norm || !gy_video || !gy_text) return fail(CROSSCLR_E_ARG, "NULL argument");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "crossclr_project_backward_prep needs the register-resident path");
-#else
     if (plan->mode != CROSSCLR_MODE_BF16) return fail(CROSSCLR_E_ARG, "crossclr_project_backward_prep: bf16 plans only");
     if (ld_gv < plan->D || ld_gt < plan->D || ld_out < plan->D) return fail(CROSSCLR_E_ARG, "row stride smaller than D");
     Geo g; memset(&g, 0, sizeof(g));
@@ -530,7 +518,6 @@ extern "C" int crossclr_project_backward_prep(const crossclr_plan* plan, const f
     LAUNCH(project_backward_prep_kernel, dim3((plan->b + 3) / 4), dim3(256), stream, g_video, g_text, ld_gv, ld_gt, g, (const bf16_t*)xhat,
            inv_norm, gy_video, gy_text, ld_out);
     return launch_status("project_backward_prep_kernel");
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -543,173 +530,193 @@ static int unpack_k(const crossclr_sample_weights* sw, const float** krows, cons
     return CROSSCLR_OK;
 }
 
-// generic tiled forward: MODE 0 sums with the common shift, 1 row maxima, 2 sums with per-row shifts
-template <typename T>
-static void forward_generic_t(const crossclr_plan* plan, const Geo& g, const void* rows, const void* cols, float* out,
-                              const float* kcols, const float* shift, int mode, int tps, dim3 grid, void* stream) {
-    dim3 block(256);
-    (void)plan;
-#define CROSSCLR_LFG(SW, MODE) LAUNCH((fwd_sums_kernel<T, SW, MODE>), grid, block, stream, (const T*)rows, (const T*)cols, g, tps, out, kcols, shift, (float*)nullptr, (int*)nullptr, (float*)nullptr)
-    if (kcols) { if (mode == 0) CROSSCLR_LFG(true, 0); else if (mode == 1) CROSSCLR_LFG(true, 1); else CROSSCLR_LFG(true, 2); }
-    else { if (mode == 0) CROSSCLR_LFG(false, 0); else if (mode == 1) CROSSCLR_LFG(false, 1); else CROSSCLR_LFG(false, 2); }
-#undef CROSSCLR_LFG
+// ---- fwd_sums_kernel<T, SW, MODE, ST, SYM>: one descriptor, one launcher ---------------------------------------------------------
+// the pass = the kernel's MODE: sums with the common shift, row maxima, sums with per-row shifts; the two score-statistics modes
+enum class FwdPass { Sums = 0, RowMax = 1, ShiftedSums = 2, ScoreRows = 3, ScoreDiag = 4 };
+struct FwdSums {
+    FwdPass pass;
+    bool save;                 // ST: leave the exponentials in `stash` (Sums and ShiftedSums only)
+    bool symmetric;            // SYM: rows == cols, upper triangle + column partials (ScoreRows: one pass for both directions)
+    const void *rows, *cols;
+    float* out;
+    const float* kcols;        // SW: the columns' negative scales
+    const float* shift;        // ShiftedSums: the rows' shifts; score modes: the positive-pair scores
+    const float* shift_cols;   // save && ShiftedSums && !symmetric: the columns' shifts, for the transposed records behind the direct ones
+    float* stash;              // save: the exponentials; ScoreRows: the active counts
+    int* header;               // symmetric: the launch group's header; ScoreRows: the optional hinge mask
+    float* colpart;            // symmetric: the column partials
+};
+// a pass over every tile of rows x cols / over the upper triangle of the local block x against itself
+static FwdSums full_pass(FwdPass pass, const void* rows, const void* cols, float* out, const float* kcols, const float* shift) {
+    return {pass, false, false, rows, cols, out, kcols, shift, nullptr, nullptr, nullptr, nullptr};
 }
-// symmetric evaluation of the local block by the generic forward (rows == columns): upper triangle + column sums; `shift` != NULL:
-// the second pass of the two-pass soft-max (sums relative to per-row shifts); `stash` != NULL (exact-fp32 plans): save the exponentials
+static FwdSums symmetric_pass(FwdPass pass, const void* x, const FwdSlot& s, const float* k, const float* shift) {
+    return {pass, false, true, x, x, s.out, k, shift, nullptr, nullptr, s.header, s.colpart};
+}
+static FwdSums saving(FwdSums d, void* stash, const float* shift_cols = nullptr) {
+    d.save = true; d.stash = static_cast<float*>(stash); d.shift_cols = shift_cols;
+    return d;
+}
+// crossclr_last_kernel(0): bf16 plans save 2-byte records, the others fp32 fragments; the split-operand instantiations carry <x3_t>
+template <typename T> static const char* fwd_sums_label(const FwdSums& d) {
+    constexpr bool x3 = std::is_same<T, x3_t>::value;
+    if (d.pass == FwdPass::ScoreDiag) return "fwd_sums_kernel (positive-pair scores)";
+    if (d.pass == FwdPass::ScoreRows) return "fwd_sums_kernel (score rows)";
+    if (d.save && sizeof(T) == 2)
+        return d.symmetric ? "fwd_sums_kernel (symmetric, save, bf16 records)"
+                           : (d.pass == FwdPass::Sums ? "fwd_sums_kernel (rectangular, save, bf16 records)" : "fwd_sums_kernel (save, bf16 records)");
+    if (d.symmetric)
+        return d.save ? (x3 ? "fwd_sums_kernel<x3_t> (symmetric, save)" : "fwd_sums_kernel (symmetric, save)")
+                      : (x3 ? "fwd_sums_kernel<x3_t> (symmetric)" : "fwd_sums_kernel (symmetric)");
+    return d.save ? (x3 ? "fwd_sums_kernel<x3_t> (save)" : "fwd_sums_kernel (save)") : (x3 ? "fwd_sums_kernel<x3_t>" : "fwd_sums_kernel");
+}
+template <typename T, bool SW, int MODE, bool ST, bool SYM>
+static void launch_fwd_sums_as(const crossclr_plan* plan, const Geo& g, const FwdSums& d, void* stream) {
+    const int nsplit = MODE == 4 ? 1 : plan->fwd_slots;
+    // rows: 128-row blocks; symmetric: one blockIdx.x per PAIR of row blocks (I, ntiles - 1 - I), which walks its tiles without a
+    // tiles-per-split; ScoreRows in one pass: the rows of modality 0 against the column tiles of modality 1
+    const int row_blocks = SYM ? (MODE == 3 ? plan->bpad / 128 : 2 * plan->bpad / 256) : 2 * plan->bpad / 128;
+    const int ntiles = SYM ? (MODE == 3 ? plan->bpad / 128 : 0) : g.col_ranks * 2 * plan->bpad / 128;
+    LAUNCH((fwd_sums_kernel<T, SW, MODE, ST, SYM>), dim3(row_blocks, nsplit), dim3(256), stream, (const T*)d.rows, (const T*)d.cols, g,
+           (ntiles + nsplit - 1) / nsplit, d.out, d.kcols, d.shift, d.stash, d.header, SYM ? d.colpart : const_cast<float*>(d.shift_cols));
+}
+// grid, tiles per split and template arguments from the descriptor; only the combinations the kernel's static_asserts allow (and, of the
+// score modes, only what the score entry points use: no scales, no split operand) are instantiated
 template <typename T>
-static int forward_generic_sym(const crossclr_plan* plan, const Geo& g, const void* x, float* out, const float* k, float* colpart,
-                               int* header, void* stream, float* stash = nullptr, const float* shift = nullptr, bool rowmax = false) {
-    dim3 grid(2 * plan->bpad / 256, plan->fwd_slots), block(256);     // one blockIdx.x per PAIR of row blocks (I, ntiles - 1 - I)
-#define CROSSCLR_LSY(TT, SW, MODE, ST) \
-    LAUNCH((fwd_sums_kernel<TT, SW, MODE, ST, true>), grid, block, stream, (const TT*)x, (const TT*)x, g, 0, out, k, shift, stash, header, colpart)
-    if (stash) {   // exact-fp32 plans (T = float: fp32 fragments, both triangles) or wide bf16 plans (bf16 records, upper triangle)
-        if constexpr (sizeof(T) == 2) {
-            if (shift) return fail(CROSSCLR_E_ARG, "bf16 plans save their exponentials in the single-pass soft-max only");
-            if (k) CROSSCLR_LSY(bf16_t, true, 0, true); else CROSSCLR_LSY(bf16_t, false, 0, true);
-            return launch_status("fwd_sums_kernel (symmetric, save, bf16 records)");
-        } else {
-            if (shift) { if (k) CROSSCLR_LSY(T, true, 2, true); else CROSSCLR_LSY(T, false, 2, true); }
-            else { if (k) CROSSCLR_LSY(T, true, 0, true); else CROSSCLR_LSY(T, false, 0, true); }
-            return launch_status(glabel<T>("fwd_sums_kernel (symmetric, save)", "fwd_sums_kernel<x3_t> (symmetric, save)"));
+static int launch_fwd_sums(const crossclr_plan* plan, const Geo& g, const FwdSums& d, void* stream) {
+    constexpr bool records = sizeof(T) == 2;      // bf16 plans save bf16 records
+    if (d.save && records && d.symmetric && d.pass != FwdPass::Sums)
+        return fail(CROSSCLR_E_ARG, "bf16 plans save their exponentials in the single-pass soft-max only");
+    if (d.save && records && d.pass != FwdPass::Sums && d.pass != FwdPass::ShiftedSums)
+        return fail(CROSSCLR_E_ARG, "bf16 plans save through the generic forward in modes 0 (rectangular) and 2 (two-pass)");
+    const bool score = d.pass == FwdPass::ScoreRows || d.pass == FwdPass::ScoreDiag;
+    if ((d.save && d.pass != FwdPass::Sums && d.pass != FwdPass::ShiftedSums) || (score && (d.kcols || std::is_same<T, x3_t>::value)))
+        return fail(CROSSCLR_E_ARG, "fwd_sums_kernel: no instantiation for pass %d (save %d, scales %d)", (int)d.pass, (int)d.save, d.kcols != nullptr);
+    auto soft_max = [&](auto mode, auto st) {      // MODE 0 .. 2: SW x SYM at run time
+        constexpr int MODE = decltype(mode)::value;
+        constexpr bool ST = decltype(st)::value;
+        if (!d.symmetric) {
+            if (d.kcols) launch_fwd_sums_as<T, true, MODE, ST, false>(plan, g, d, stream);
+            else launch_fwd_sums_as<T, false, MODE, ST, false>(plan, g, d, stream);
+        } else if constexpr (!(ST && records && MODE == 2)) {
+            if (d.kcols) launch_fwd_sums_as<T, true, MODE, ST, true>(plan, g, d, stream);
+            else launch_fwd_sums_as<T, false, MODE, ST, true>(plan, g, d, stream);
         }
+    };
+    using std::false_type; using std::true_type; using std::integral_constant;
+    switch (d.pass) {
+        case FwdPass::Sums: if (d.save) soft_max(integral_constant<int, 0>(), true_type()); else soft_max(integral_constant<int, 0>(), false_type()); break;
+        case FwdPass::RowMax: soft_max(integral_constant<int, 1>(), false_type()); break;
+        case FwdPass::ShiftedSums: if (d.save) soft_max(integral_constant<int, 2>(), true_type()); else soft_max(integral_constant<int, 2>(), false_type()); break;
+        case FwdPass::ScoreRows:
+            if constexpr (!std::is_same<T, x3_t>::value) {
+                if (d.symmetric) launch_fwd_sums_as<T, false, 3, false, true>(plan, g, d, stream);
+                else launch_fwd_sums_as<T, false, 3, false, false>(plan, g, d, stream);
+            }
+            break;
+        case FwdPass::ScoreDiag:
+            if constexpr (!std::is_same<T, x3_t>::value) launch_fwd_sums_as<T, false, 4, false, false>(plan, g, d, stream);
+            break;
     }
-    if (rowmax) { if (k) CROSSCLR_LSY(T, true, 1, false); else CROSSCLR_LSY(T, false, 1, false); }
-    else if (shift) { if (k) CROSSCLR_LSY(T, true, 2, false); else CROSSCLR_LSY(T, false, 2, false); }
-    else { if (k) CROSSCLR_LSY(T, true, 0, false); else CROSSCLR_LSY(T, false, 0, false); }
-#undef CROSSCLR_LSY
-    return launch_status(glabel<T>("fwd_sums_kernel (symmetric)", "fwd_sums_kernel<x3_t> (symmetric)"));
+    return launch_status(fwd_sums_label<T>(d));
+}
+// the soft-max passes: the operand type from the plan
+static int fwd_sums(const crossclr_plan* plan, const Geo& g, const FwdSums& d, void* stream) {
+    return with_plan_type(plan, [&](auto t) { return launch_fwd_sums<typename decltype(t)::type>(plan, g, d, stream); });
 }
 
-static int forward_generic(const crossclr_plan* plan, const Geo& g, const void* rows, const void* cols, float* out,
-                           const float* kcols, const float* shift, int mode, void* stream, float* stash, const float* shift_cols) {
-    const int ntiles = g.col_ranks * 2 * plan->bpad / 128;
-    const int nsplit = plan->fwd_slots;
-    const int tps = (ntiles + nsplit - 1) / nsplit;
-    dim3 grid(2 * plan->bpad / 128, nsplit);
-    if (stash && plan->mode == CROSSCLR_MODE_BF16) {   // two-pass regime of a bf16 plan: the full second pass leaves bf16 records (rectangular layout)
-        dim3 block(256);
-        if (mode == 0) {   // wide plans, this rank's rows against other ranks' columns: every tile's record, rectangular layout
-            if (kcols) LAUNCH((fwd_sums_kernel<bf16_t, true, 0, true>), grid, block, stream, (const bf16_t*)rows, (const bf16_t*)cols, g, tps, out, kcols, shift, stash, (int*)nullptr, (float*)nullptr);
-            else LAUNCH((fwd_sums_kernel<bf16_t, false, 0, true>), grid, block, stream, (const bf16_t*)rows, (const bf16_t*)cols, g, tps, out, kcols, shift, stash, (int*)nullptr, (float*)nullptr);
-            return launch_status("fwd_sums_kernel (rectangular, save, bf16 records)");
-        }
-        if (mode != 2) return fail(CROSSCLR_E_ARG, "bf16 plans save through the generic forward in modes 0 (rectangular) and 2 (two-pass)");
-        if (kcols) LAUNCH((fwd_sums_kernel<bf16_t, true, 2, true>), grid, block, stream, (const bf16_t*)rows, (const bf16_t*)cols, g, tps, out, kcols, shift, stash, (int*)nullptr, const_cast<float*>(shift_cols));
-        else LAUNCH((fwd_sums_kernel<bf16_t, false, 2, true>), grid, block, stream, (const bf16_t*)rows, (const bf16_t*)cols, g, tps, out, kcols, shift, stash, (int*)nullptr, const_cast<float*>(shift_cols));
-        return launch_status("fwd_sums_kernel (save, bf16 records)");
-    }
-    if (stash) {   // exact-fp32 forward that also saves its exponentials (local block; common shift, or per-row shifts: mode 2)
-        dim3 block(256);
-#define CROSSCLR_LSV(TT, SW, MODE) LAUNCH((fwd_sums_kernel<TT, SW, MODE, true>), grid, block, stream, (const TT*)rows, (const TT*)cols, g, tps, out, kcols, shift, stash, (int*)nullptr, const_cast<float*>(mode == 2 ? shift_cols : nullptr))
-        if (is_x3(plan)) {   // split operand, the same fp32 stash
-            if (mode == 2) { if (kcols) CROSSCLR_LSV(x3_t, true, 2); else CROSSCLR_LSV(x3_t, false, 2); }
-            else { if (kcols) CROSSCLR_LSV(x3_t, true, 0); else CROSSCLR_LSV(x3_t, false, 0); }
-            return launch_status("fwd_sums_kernel<x3_t> (save)");
-        }
-        if (mode == 2) { if (kcols) CROSSCLR_LSV(float, true, 2); else CROSSCLR_LSV(float, false, 2); }
-        else { if (kcols) CROSSCLR_LSV(float, true, 0); else CROSSCLR_LSV(float, false, 0); }
-#undef CROSSCLR_LSV
-        return launch_status("fwd_sums_kernel (save)");
-    }
-    if (plan->mode == CROSSCLR_MODE_FP32) forward_generic_t<float>(plan, g, rows, cols, out, kcols, shift, mode, tps, grid, stream);
-    else if (is_x3(plan)) {
-        forward_generic_t<x3_t>(plan, g, rows, cols, out, kcols, shift, mode, tps, grid, stream);
-        return launch_status("fwd_sums_kernel<x3_t>");
-    } else forward_generic_t<bf16_t>(plan, g, rows, cols, out, kcols, shift, mode, tps, grid, stream);
-    return launch_status("fwd_sums_kernel");
+// the local block evaluated against itself (the single-device case, or the local block of a sharded run): upper triangle + column sums.
+// The generic kernels scale the mirrored tiles with the ROWS' array, so their callers also require krows == kcols.
+static bool is_local_symmetric_block(const crossclr_plan* plan, const Geo& g, const void* rows, const void* cols) {
+    return rows == cols && g.col_ranks == 1 && g.col_rank0 == plan->rank && g.skip_rank < 0 && !env_knobs().disable_symmetric;
 }
 
 extern "C" int crossclr_forward(const crossclr_plan* plan, const void* xhat_rows, const void* xhat_cols,
                                 int col_ranks, int col_rank0, int skip_rank, float temperature,
                                 float negative_weight, float* part, int slot0, void* stream) {
-    return crossclr_forward_w(plan, xhat_rows, xhat_cols, col_ranks, col_rank0, skip_rank, temperature, negative_weight,
-                              nullptr, part, slot0, stream);
+    return crossclr_forward_s(plan, xhat_rows, xhat_cols, col_ranks, col_rank0, skip_rank, temperature, negative_weight, nullptr, nullptr,
+                              part, slot0, stream);
 }
-
 extern "C" int crossclr_forward_w(const crossclr_plan* plan, const void* xhat_rows, const void* xhat_cols,
                                   int col_ranks, int col_rank0, int skip_rank, float temperature,
                                   float negative_weight, const crossclr_sample_weights* sw, float* part, int slot0,
                                   void* stream) {
+    return crossclr_forward_s(plan, xhat_rows, xhat_cols, col_ranks, col_rank0, skip_rank, temperature, negative_weight, sw, nullptr, part,
+                              slot0, stream);
+}
+// shift_rows == NULL: the single-pass soft-max (crossclr_forward_w); else the second pass of the two-pass one, on the generic kernels
+extern "C" int crossclr_forward_s(const crossclr_plan* plan, const void* xhat_rows, const void* xhat_cols, int col_ranks,
+                                  int col_rank0, int skip_rank, float temperature, float negative_weight,
+                                  const crossclr_sample_weights* sw, const float* shift_rows, float* part, int slot0, void* stream) {
     if (!plan || !xhat_rows || !xhat_cols || !part || slot0 < 0) return fail(CROSSCLR_E_ARG, "NULL/negative argument");
     const float *krows, *kcols;
     if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
     Geo g;
-    int rc = make_geo(plan, col_ranks, col_rank0, skip_rank, temperature, negative_weight, &g);
+    int rc = make_geo(plan, col_ranks, col_rank0, skip_rank, temperature, negative_weight, &g, shift_rows != nullptr);
     if (rc) return rc;
-    if (plan->fwd_slots <= 0 || slot0 % plan->fwd_slots != 0 || slot0 / plan->fwd_slots >= kLaunchGroups)
-        return fail(CROSSCLR_E_ARG, "slot0 must be L * plan->fwd_slots, L = 0..%d", kLaunchGroups - 1);
-    float* out = part + (size_t)slot0 * 2 * plan->bpad;
-    int* header = reinterpret_cast<int*>(part + ws_flag_off(plan)) + 4 * (slot0 / plan->fwd_slots);
-#ifndef CROSSCLR_NO_FAST
-    if (plan->fast_path) {
-        // rows and columns are the same packed operand (the single-GPU case and the local block of a
-        // sharded run): evaluate only the upper triangle of the symmetric matrix
-        const bool symmetric = xhat_rows == xhat_cols && col_ranks == 1 && col_rank0 == plan->rank && skip_rank < 0 &&
-                               !env_knobs().disable_symmetric;
-        const bool skipping = skip_rank >= col_rank0 && skip_rank < col_rank0 + col_ranks;
-        if (col_ranks - (skipping ? 1 : 0) <= 0) {
+    FwdSlot s;
+    if ((rc = fwd_slot(plan, part, slot0, &s))) return rc;
+    const bool local = is_local_symmetric_block(plan, g, xhat_rows, xhat_cols);
+    const size_t out_bytes = (size_t)plan->fwd_slots * 2 * plan->bpad * sizeof(float);
+    if (plan->fast_path && !shift_rows) {
+        if (usable_col_ranks(g) <= 0) {
             // nothing to do (every column rank is skipped): leave a dense, all-zero launch behind
-            rc = device_zero_header(header, stream);
-            if (rc) return rc;
-            return device_zero(out, (size_t)plan->fwd_slots * 2 * plan->bpad * sizeof(float), stream);
+            rc = device_zero_header(s.header, stream);
+            return rc ? rc : device_zero(s.out, out_bytes, stream);
         }
-        rc = fast_forward(plan, g, xhat_rows, xhat_cols, out, part + ws_colpart_off(plan), header, symmetric, krows, kcols, stream);
+        rc = fast_forward(plan, g, xhat_rows, xhat_cols, s.out, s.colpart, s.header, local, krows, kcols, stream);
         return rc ? fail(rc, "fast_forward: unsupported Dpad %d", plan->Dpad) : launch_status("fast_fwd_kernel");
     }
-#endif
-    if (xhat_rows == xhat_cols && col_ranks == 1 && col_rank0 == plan->rank && skip_rank < 0 && krows == kcols &&
-        !env_knobs().disable_symmetric) {
-        // the local block (single device, or the local block of a sharded run), forward only: upper triangle + column sums
-        float* colpart = part + ws_colpart_off(plan);
-        if (is_x3(plan)) return forward_generic_sym<x3_t>(plan, g, xhat_rows, out, kcols, colpart, header, stream);
-        return plan->mode == CROSSCLR_MODE_FP32 ? forward_generic_sym<float>(plan, g, xhat_rows, out, kcols, colpart, header, stream)
-                                                : forward_generic_sym<bf16_t>(plan, g, xhat_rows, out, kcols, colpart, header, stream);
+    // the second pass marks its launch group dense up front, before the symmetric launch too, and returns early when every column rank is
+    // skipped; the single pass on the generic kernels does so only in front of a full launch, which it enqueues even over no columns
+    if (shift_rows) {
+        if ((rc = device_zero_header(s.header, stream))) return rc;
+        if (usable_col_ranks(g) <= 0) return device_zero(s.out, out_bytes, stream);
     }
-    rc = device_zero_header(header, stream);
-    if (rc) return rc;
-    return forward_generic(plan, g, xhat_rows, xhat_cols, out, kcols, nullptr, 0, stream);
+    const FwdPass pass = shift_rows ? FwdPass::ShiftedSums : FwdPass::Sums;
+    if (local && krows == kcols) return fwd_sums(plan, g, symmetric_pass(pass, xhat_rows, s, kcols, shift_rows), stream);
+    if (!shift_rows && (rc = device_zero_header(s.header, stream))) return rc;
+    return fwd_sums(plan, g, full_pass(pass, xhat_rows, xhat_cols, s.out, kcols, shift_rows), stream);
 }
 
+// what the saved backwards of the LOCAL block share: the sample weights (the rows' and the columns' negative scales are one array) and the
+// geometry; two_pass: per-row shifts allowed
+static int local_saved_args(const crossclr_plan* plan, const crossclr_sample_weights* sw, float temperature, float negative_weight,
+                            bool two_pass, const float** k, Geo* g) {
+    const float* kcols;
+    if (int rk = unpack_k(sw, k, &kcols)) return rk;
+    if (*k != kcols) return fail(CROSSCLR_E_ARG, "the local block's row and column negative scales are the same array");
+    return make_geo(plan, 1, plan->rank, -1, temperature, negative_weight, g, two_pass);
+}
+// what the saving forwards of the LOCAL block share beyond local_saved_args: the launch group of the workspace
+static int local_save_args(const crossclr_plan* plan, const crossclr_sample_weights* sw, float temperature, float negative_weight, bool two_pass,
+                           float* part, int slot0, const float** k, Geo* g, FwdSlot* s) {
+    if (int rc = local_saved_args(plan, sw, temperature, negative_weight, two_pass, k, g)) return rc;
+    return fwd_slot(plan, part, slot0, s);
+}
 extern "C" int crossclr_forward_save(const crossclr_plan* plan, const void* xhat, float temperature, float negative_weight,
                                      const crossclr_sample_weights* sw, float* part, int slot0, void* stash, void* stream) {
     if (!plan || !xhat || !part || !stash || slot0 < 0) return fail(CROSSCLR_E_ARG, "NULL/negative argument");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "crossclr_forward_save needs the register-resident path");
-#else
     if (!plan->stash_bytes) return fail(CROSSCLR_E_ARG, "this plan has no save-for-backward path (stash_bytes == 0)");
-    const float *krows, *kcols;
-    if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
-    if (krows != kcols) return fail(CROSSCLR_E_ARG, "the local block's row and column negative scales are the same array");
+    const float* k;
     Geo g;
-    int rc = make_geo(plan, 1, plan->rank, -1, temperature, negative_weight, &g);
+    FwdSlot s;
+    int rc = local_save_args(plan, sw, temperature, negative_weight, false, part, slot0, &k, &g, &s);
     if (rc) return rc;
-    if (plan->fwd_slots <= 0 || slot0 % plan->fwd_slots != 0 || slot0 / plan->fwd_slots >= kLaunchGroups)
-        return fail(CROSSCLR_E_ARG, "slot0 must be L * plan->fwd_slots, L = 0..%d", kLaunchGroups - 1);
-    float* out = part + (size_t)slot0 * 2 * plan->bpad;
-    int* header = reinterpret_cast<int*>(part + ws_flag_off(plan)) + 4 * (slot0 / plan->fwd_slots);
-    if (!plan->fast_path && plan->mode == CROSSCLR_MODE_BF16)   // wide bf16 plan: upper triangle, bf16 records in the register-resident layout
-        return forward_generic_sym<bf16_t>(plan, g, xhat, out, kcols, part + ws_colpart_off(plan), header, stream, static_cast<float*>(stash));
-    if (!plan->fast_path) {   // exact-fp32 mode (and BF16X3: the same launch on the split operand)
-        if (!env_knobs().disable_symmetric)   // upper triangle; every fragment stored twice (as evaluated + transposed)
-            return is_x3(plan) ? forward_generic_sym<x3_t>(plan, g, xhat, out, kcols, part + ws_colpart_off(plan), header, stream, static_cast<float*>(stash))
-                               : forward_generic_sym<float>(plan, g, xhat, out, kcols, part + ws_colpart_off(plan), header, stream, static_cast<float*>(stash));
-        rc = device_zero_header(header, stream);
-        if (rc) return rc;
-        return forward_generic(plan, g, xhat, xhat, out, kcols, nullptr, 0, stream, static_cast<float*>(stash));
+    if (plan->fast_path) {
+        rc = fast_forward_save(plan, g, xhat, s.out, s.colpart, s.header, k, stash, stream);
+        return rc ? fail(rc, "fast_forward_save: unsupported Dpad %d", plan->Dpad) : launch_status("fast_fwd_kernel (save)");
     }
-    rc = fast_forward_save(plan, g, xhat, out, part + ws_colpart_off(plan), header, krows, stash, stream);
-    return rc ? fail(rc, "fast_forward_save: unsupported Dpad %d", plan->Dpad) : launch_status("fast_fwd_kernel (save)");
-#endif
+    // wide bf16 plans: upper triangle, bf16 records in the register-resident layout; exact-fp32 mode (and BF16X3: the same launch on the
+    // split operand): upper triangle, every fragment stored twice (as evaluated + transposed)
+    if (plan->mode == CROSSCLR_MODE_BF16 || !env_knobs().disable_symmetric)
+        return fwd_sums(plan, g, saving(symmetric_pass(FwdPass::Sums, xhat, s, k, nullptr), stash), stream);
+    if ((rc = device_zero_header(s.header, stream))) return rc;
+    return fwd_sums(plan, g, saving(full_pass(FwdPass::Sums, xhat, xhat, s.out, k, nullptr), stash), stream);
 }
 
-#ifndef CROSSCLR_NO_FAST
-// bwd_saved32_kernel / bwd_saved_x3_kernel (crossclr_kernels_saved32.h): DC columns of D per thread block -- f(std::integral_constant<int, DC>()) --
+// bwd_saved32_kernel / bwd_saved_x3_kernel (crossclr_kernels_saved32.h): DC = 256, 128 or 64 columns of D per thread block (with_d_chunk)
 // and `ntiles` 32-column tiles cut into plan->bwd_slices slices WITHOUT the even rounding of fast_backward_saved
-template <class F> static void saved32_with_dc(int Dpad, F f) {
-    if (Dpad % 256 == 0) f(std::integral_constant<int, 256>());
-    else if (Dpad % 128 == 0) f(std::integral_constant<int, 128>());
-    else f(std::integral_constant<int, 64>());
-}
 static dim3 saved32_grid(const crossclr_plan* plan, int DC) { return dim3(2 * plan->bpad / 64, plan->Dpad / DC, (unsigned)plan->bwd_slices); }
 static int saved32_tps(const crossclr_plan* plan, int ntiles) { return (ntiles + plan->bwd_slices - 1) / plan->bwd_slices; }
 
@@ -718,7 +725,7 @@ template <bool RM>
 static int backward_saved_x3(const crossclr_plan* plan, const Geo& g, const void* xhat, const void* stash, const float* rz, const float* wrz,
                              const float* k, float* gbuf, int accumulate, void* stream) {
     const int tps = saved32_tps(plan, 2 * plan->bpad / 32);
-    saved32_with_dc(plan->Dpad, [&](auto dc) {
+    with_d_chunk<256, 128, 64>(plan->Dpad, [&](auto dc) {
         constexpr int DC = decltype(dc)::value;
         if (k) LAUNCH((bwd_saved_x3_kernel<DC, true, RM>), saved32_grid(plan, DC), dim3(256), stream, (const x3_t*)xhat, (const float*)stash, g, rz,
                       wrz, gbuf, accumulate, tps, k);
@@ -734,7 +741,7 @@ static int launch_saved32(const crossclr_plan* plan, const Geo& g, const void* x
                           const float* rzc, const float* wrzc, const float* k, const float* kc, int ntiles, float* gbuf, int accumulate,
                           void* stream) {
     const int tps = saved32_tps(plan, ntiles);
-    saved32_with_dc(plan->Dpad, [&](auto dc) {
+    with_d_chunk<256, 128, 64>(plan->Dpad, [&](auto dc) {
         constexpr int DC = decltype(dc)::value;
         if (k) LAUNCH((bwd_saved32_kernel<DC, true, RM, RECT>), saved32_grid(plan, DC), dim3(256), stream, (const float*)x, (const float*)stash, g,
                       rz, wrz, gbuf, accumulate, tps, k, rzc, wrzc, kc);
@@ -764,26 +771,12 @@ static Geo transposed_geo(const crossclr_plan* plan, Geo g, int segments, int wh
     g.col_ranks = segments; g.skip_rank = which; g.col_rank0 = plan->rank; g.col_wrap = 0; g.row_rank = row_rank;
     return g;
 }
-#endif
-
-// what the saved backwards of the LOCAL block share: the sample weights (the rows' and the columns' negative scales are one array) and the
-// geometry; two_pass: per-row shifts allowed
-static int local_saved_args(const crossclr_plan* plan, const crossclr_sample_weights* sw, float temperature, float negative_weight,
-                            bool two_pass, const float** k, Geo* g) {
-    const float* kcols;
-    if (int rk = unpack_k(sw, k, &kcols)) return rk;
-    if (*k != kcols) return fail(CROSSCLR_E_ARG, "the local block's row and column negative scales are the same array");
-    return make_geo(plan, 1, plan->rank, -1, temperature, negative_weight, g, two_pass);
-}
 
 // crossclr_backward_saved (RowMajor), _saved_xf (FragmentOne) and _saved_xfp (FragmentPair); fn: the entry point's name, for its refusals
 static int backward_saved_local(const char* fn, SavedOperand operand, const crossclr_plan* plan, const void* x, const void* stash,
                                 float temperature, float negative_weight, const float* rz, const float* wrz,
                                 const crossclr_sample_weights* sw, float* gbuf, int accumulate, void* stream) {
     if (!plan || !x || !stash || !rz || !wrz || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "%s needs the register-resident path", fn);
-#else
     const bool row_major = operand == SavedOperand::RowMajor, pair = operand == SavedOperand::FragmentPair;
     if (row_major && !plan->stash_bytes) return fail(CROSSCLR_E_ARG, "this plan has no save-for-backward path (stash_bytes == 0)");
     if (!row_major && (!plan->stash_bytes || !plan->xf_bytes))
@@ -800,7 +793,6 @@ static int backward_saved_local(const char* fn, SavedOperand operand, const cros
     rc = fast_backward_saved({SavedBlock::Local, operand}, plan, g, x, stash, rz, wrz, rz, wrz, gbuf, accumulate, k, k, stream);
     if (rc) return fail(rc, "fast_backward_saved%s: unsupported Dpad %d", row_major ? "" : (pair ? " (xfp)" : " (xf)"), plan->Dpad);
     return launch_status(row_major ? "fast_bwd_dsl_kernel" : (pair ? "fast_bwd_xfp_kernel" : "fast_bwd_dsl_kernel (xf)"));
-#endif
 }
 extern "C" int crossclr_backward_saved(const crossclr_plan* plan, const void* xhat, const void* stash, float temperature,
                                        float negative_weight, const float* rz, const float* wrz,
@@ -826,14 +818,11 @@ extern "C" int crossclr_forward_pairs(const crossclr_plan* plan, const void* xha
                                       const crossclr_sample_weights* sw, float* part, int slot0, float* colsum_out,
                                       void* stream) {
     if (!plan || !xhat_rows || !xhat_all || !part || !colsum_out) return fail(CROSSCLR_E_ARG, "NULL argument");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "crossclr_forward_pairs needs the register-resident path");
-#else
     if (!plan->fast_path) return fail(CROSSCLR_E_ARG, "crossclr_forward_pairs needs the register-resident bf16 path");
     if (first_rank < 0 || first_rank >= plan->world || nranks < 1 || nranks > (plan->world - 1) / 2)
         return fail(CROSSCLR_E_ARG, "bad first_rank/nranks %d/%d for world %d", first_rank, nranks, plan->world);
-    if (plan->fwd_slots <= 0 || slot0 < 0 || slot0 % plan->fwd_slots != 0 || slot0 / plan->fwd_slots >= kLaunchGroups)
-        return fail(CROSSCLR_E_ARG, "slot0 must be L * plan->fwd_slots, L = 0..%d", kLaunchGroups - 1);
+    FwdSlot s;
+    if (int rs = fwd_slot(plan, part, slot0, &s)) return rs;
     for (int i = 0; i < nranks; ++i)
         if ((first_rank + i) % plan->world == plan->rank) return fail(CROSSCLR_E_ARG, "the pair range must not contain this rank");
     const float *krows, *kcols;
@@ -842,61 +831,23 @@ extern "C" int crossclr_forward_pairs(const crossclr_plan* plan, const void* xha
     int rc = make_geo(plan, nranks, first_rank, -1, temperature, negative_weight, &g);
     if (rc) return rc;
     g.col_wrap = plan->world;
-    float* out = part + (size_t)slot0 * 2 * plan->bpad;
-    int* header = reinterpret_cast<int*>(part + ws_flag_off(plan)) + 4 * (slot0 / plan->fwd_slots);
-    float* colpart = part + ws_paircol_off(plan);
-    rc = fast_forward(plan, g, xhat_rows, xhat_all, out, colpart, header, false, krows, kcols, stream, true);
+    rc = fast_forward(plan, g, xhat_rows, xhat_all, s.out, s.paircol, s.header, false, krows, kcols, stream, true);
     if (rc) return fail(rc, "fast_forward: unsupported Dpad %d", plan->Dpad);
     const int nrb = 2 * plan->bpad / (32 * fast_fwd_tpr(plan->Dpad));
     const int ncols = nranks * 2 * plan->bpad;
-    LAUNCH(colsum_reduce_kernel, dim3((ncols + 255) / 256), dim3(256), stream, (const float*)colpart, nrb, ncols, colsum_out);
+    LAUNCH(colsum_reduce_kernel, dim3((ncols + 255) / 256), dim3(256), stream, (const float*)s.paircol, nrb, ncols, colsum_out);
     return launch_status("fast_fwd_kernel (pairs)");
-#endif
 }
 
 extern "C" int crossclr_forward_add(const crossclr_plan* plan, float* part, int slot0, const float* vec, void* stream) {
     if (!plan || !part) return fail(CROSSCLR_E_ARG, "NULL argument");
-    if (plan->fwd_slots <= 0 || slot0 < 0 || slot0 % plan->fwd_slots != 0 || slot0 / plan->fwd_slots >= kLaunchGroups)
-        return fail(CROSSCLR_E_ARG, "slot0 must be L * plan->fwd_slots, L = 0..%d", kLaunchGroups - 1);
+    FwdSlot s;
+    if (int rc = fwd_slot(plan, part, slot0, &s)) return rc;
     const int n = 2 * plan->bpad;
-    LAUNCH(fwd_add_kernel, dim3((n + 255) / 256), dim3(256), stream, vec, n, part + (size_t)slot0 * n,
-           reinterpret_cast<int*>(part + ws_flag_off(plan)) + 4 * (slot0 / plan->fwd_slots));
+    LAUNCH(fwd_add_kernel, dim3((n + 255) / 256), dim3(256), stream, vec, n, s.out, s.header);
     return launch_status("fwd_add_kernel");
 }
 
-extern "C" int crossclr_forward_finish(const crossclr_plan* plan, const float* part, int nslots,
-                                       const float* diag_cos, float temperature, float negative_weight,
-                                       float* logz, float* rz, float* wrz, double* loss_sum, void* stream) {
-    return crossclr_forward_finish_w(plan, part, nslots, diag_cos, temperature, negative_weight, nullptr, logz, rz, wrz,
-                                     loss_sum, stream);
-}
-
-extern "C" int crossclr_forward_finish_w(const crossclr_plan* plan, const float* part, int nslots,
-                                         const float* diag_cos, float temperature, float negative_weight,
-                                         const crossclr_sample_weights* sw, float* logz, float* rz, float* wrz,
-                                         double* loss_sum, void* stream) {
-    if (!plan || !part || !diag_cos || !logz || !rz || !wrz || !loss_sum || plan->fwd_slots <= 0 || nslots <= 0 ||
-        nslots % plan->fwd_slots != 0 || nslots / plan->fwd_slots > kLaunchGroups)
-        return fail(CROSSCLR_E_ARG, "NULL argument / nslots must be fwd_slots times the number of launch groups (1..%d)", kLaunchGroups);
-    Geo g;
-    int rc = make_geo(plan, 1, plan->rank, -1, temperature, negative_weight, &g);
-    if (rc) return rc;
-    const int nb = plan->loss_ws_doubles - 1;
-    const int nlaunch = nslots / plan->fwd_slots;
-    return crossclr_forward_finish_s(plan, part, nslots, diag_cos, temperature, negative_weight, sw, nullptr, logz, rz, wrz, loss_sum,
-                                     stream);
-}
-
-static int forward_finish_impl(const crossclr_plan* plan, const float* part, int nslots,
-                               const float* diag_cos, float temperature, float negative_weight,
-                               const crossclr_sample_weights* sw, const float* shift_rows, float* logz, float* rz,
-                               float* wrz, double* loss_sum, void* stream, int* ticket);
-extern "C" int crossclr_forward_finish_s(const crossclr_plan* plan, const float* part, int nslots,
-                                         const float* diag_cos, float temperature, float negative_weight,
-                                         const crossclr_sample_weights* sw, const float* shift_rows, float* logz, float* rz,
-                                         float* wrz, double* loss_sum, void* stream) {
-    return forward_finish_impl(plan, part, nslots, diag_cos, temperature, negative_weight, sw, shift_rows, logz, rz, wrz, loss_sum, stream, nullptr);
-}
 // ticket != NULL (crossclr_step_forward; an int the step's first kernel has cleared): the finish kernel's last block forms the sum -- one launch
 static int forward_finish_impl(const crossclr_plan* plan, const float* part, int nslots,
                                const float* diag_cos, float temperature, float negative_weight,
@@ -919,6 +870,23 @@ static int forward_finish_impl(const crossclr_plan* plan, const float* part, int
     if (!ticket) LAUNCH(fwd_finish_reduce_kernel, dim3(1), dim3(64), stream, loss_sum, nb, 1.0 / (2.0 * (double)plan->b * (double)plan->world));
     return launch_status("fwd_finish_kernel");
 }
+extern "C" int crossclr_forward_finish(const crossclr_plan* plan, const float* part, int nslots,
+                                       const float* diag_cos, float temperature, float negative_weight,
+                                       float* logz, float* rz, float* wrz, double* loss_sum, void* stream) {
+    return forward_finish_impl(plan, part, nslots, diag_cos, temperature, negative_weight, nullptr, nullptr, logz, rz, wrz, loss_sum, stream, nullptr);
+}
+extern "C" int crossclr_forward_finish_w(const crossclr_plan* plan, const float* part, int nslots,
+                                         const float* diag_cos, float temperature, float negative_weight,
+                                         const crossclr_sample_weights* sw, float* logz, float* rz, float* wrz,
+                                         double* loss_sum, void* stream) {
+    return forward_finish_impl(plan, part, nslots, diag_cos, temperature, negative_weight, sw, nullptr, logz, rz, wrz, loss_sum, stream, nullptr);
+}
+extern "C" int crossclr_forward_finish_s(const crossclr_plan* plan, const float* part, int nslots,
+                                         const float* diag_cos, float temperature, float negative_weight,
+                                         const crossclr_sample_weights* sw, const float* shift_rows, float* logz, float* rz,
+                                         float* wrz, double* loss_sum, void* stream) {
+    return forward_finish_impl(plan, part, nslots, diag_cos, temperature, negative_weight, sw, shift_rows, logz, rz, wrz, loss_sum, stream, nullptr);
+}
 
 // ---- two-pass soft-max for small temperatures (max |logit| > 128) ------------------------------------------------------
 extern "C" int crossclr_needs_row_shift(float temperature, float negative_weight) {
@@ -935,54 +903,17 @@ extern "C" int crossclr_forward_rowmax(const crossclr_plan* plan, const void* xh
     Geo g;
     int rc = make_geo(plan, col_ranks, col_rank0, skip_rank, temperature, negative_weight, &g, true);
     if (rc) return rc;
-    const bool skipping = skip_rank >= col_rank0 && skip_rank < col_rank0 + col_ranks;
     const int n = 2 * plan->bpad;
     int nslots = plan->fwd_slots;
     const float* colpart = nullptr;
-    if (col_ranks - (skipping ? 1 : 0) <= 0) nslots = 0;   // nothing to look at: only the self pair / the previous value
-    else if (xhat_rows == xhat_cols && col_ranks == 1 && col_rank0 == plan->rank && skip_rank < 0 && krows == kcols &&
-             !env_knobs().disable_symmetric) {   // the local block: upper triangle, column maxima for the mirrored tiles
-        float* cp = part + ws_colpart_off(plan);
-        int* header = reinterpret_cast<int*>(part + ws_flag_off(plan));   // (launch group 0's header: rewritten by the pass that follows)
-        rc = is_x3(plan) ? forward_generic_sym<x3_t>(plan, g, xhat_rows, part, kcols, cp, header, stream, nullptr, nullptr, true)
-           : plan->mode == CROSSCLR_MODE_FP32 ? forward_generic_sym<float>(plan, g, xhat_rows, part, kcols, cp, header, stream, nullptr, nullptr, true)
-                                              : forward_generic_sym<bf16_t>(plan, g, xhat_rows, part, kcols, cp, header, stream, nullptr, nullptr, true);
-        if (rc) return rc;
-        colpart = cp;
-    } else if ((rc = forward_generic(plan, g, xhat_rows, xhat_cols, part, kcols, nullptr, 1, stream))) return rc;
+    if (usable_col_ranks(g) <= 0) nslots = 0;   // nothing to look at: only the self pair / the previous value
+    else if (is_local_symmetric_block(plan, g, xhat_rows, xhat_cols) && krows == kcols) {   // upper triangle, column maxima for the mirrored tiles
+        const FwdSlot s = fwd_group(plan, part, 0);   // (launch group 0 and its header: rewritten by the pass that follows)
+        if ((rc = fwd_sums(plan, g, symmetric_pass(FwdPass::RowMax, xhat_rows, s, kcols, nullptr), stream))) return rc;
+        colpart = s.colpart;
+    } else if ((rc = fwd_sums(plan, g, full_pass(FwdPass::RowMax, xhat_rows, xhat_cols, part, kcols, nullptr), stream))) return rc;
     LAUNCH(rowmax_combine_kernel, dim3((n + 255) / 256), dim3(256), stream, (const float*)part, nslots, n, krows, accumulate, shift_rows, colpart);
     return launch_status("rowmax_combine_kernel");
-}
-
-extern "C" int crossclr_forward_s(const crossclr_plan* plan, const void* xhat_rows, const void* xhat_cols, int col_ranks,
-                                  int col_rank0, int skip_rank, float temperature, float negative_weight,
-                                  const crossclr_sample_weights* sw, const float* shift_rows, float* part, int slot0, void* stream) {
-    if (!shift_rows)
-        return crossclr_forward_w(plan, xhat_rows, xhat_cols, col_ranks, col_rank0, skip_rank, temperature, negative_weight, sw, part,
-                                  slot0, stream);
-    if (!plan || !xhat_rows || !xhat_cols || !part || slot0 < 0) return fail(CROSSCLR_E_ARG, "NULL/negative argument");
-    const float *krows, *kcols;
-    if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
-    Geo g;
-    int rc = make_geo(plan, col_ranks, col_rank0, skip_rank, temperature, negative_weight, &g, true);
-    if (rc) return rc;
-    if (plan->fwd_slots <= 0 || slot0 % plan->fwd_slots != 0 || slot0 / plan->fwd_slots >= kLaunchGroups)
-        return fail(CROSSCLR_E_ARG, "slot0 must be L * plan->fwd_slots, L = 0..%d", kLaunchGroups - 1);
-    float* out = part + (size_t)slot0 * 2 * plan->bpad;
-    int* header = reinterpret_cast<int*>(part + ws_flag_off(plan)) + 4 * (slot0 / plan->fwd_slots);
-    rc = device_zero_header(header, stream);
-    if (rc) return rc;
-    const bool skipping = skip_rank >= col_rank0 && skip_rank < col_rank0 + col_ranks;
-    if (col_ranks - (skipping ? 1 : 0) <= 0) return device_zero(out, (size_t)plan->fwd_slots * 2 * plan->bpad * sizeof(float), stream);
-    if (xhat_rows == xhat_cols && col_ranks == 1 && col_rank0 == plan->rank && skip_rank < 0 && krows == kcols &&
-        !env_knobs().disable_symmetric) {   // the local block: upper triangle + column sums (two exponentials per element)
-        float* colpart = part + ws_colpart_off(plan);
-        if (is_x3(plan)) return forward_generic_sym<x3_t>(plan, g, xhat_rows, out, kcols, colpart, header, stream, nullptr, shift_rows);
-        return plan->mode == CROSSCLR_MODE_FP32
-                   ? forward_generic_sym<float>(plan, g, xhat_rows, out, kcols, colpart, header, stream, nullptr, shift_rows)
-                   : forward_generic_sym<bf16_t>(plan, g, xhat_rows, out, kcols, colpart, header, stream, nullptr, shift_rows);
-    }
-    return forward_generic(plan, g, xhat_rows, xhat_cols, out, kcols, shift_rows, 2, stream);
 }
 
 // the two-pass regime's save-for-backward pair (exact-fp32 plans, local block): U and Ut, twice the single-pass stash
@@ -990,13 +921,9 @@ extern "C" int crossclr_forward_s(const crossclr_plan* plan, const void* xhat_ro
 // of a one-rank remote block, followed by 2 bpad floats of zeros (crossclr_backward_saved_s passes them as the statistics of the side a
 // launch must not weigh: W = U rz_p + U^T rz_q is formed as two launches of the saved backward, direct and transposed)
 static size_t rect_bytes_s(const crossclr_plan* plan) {
-#ifdef CROSSCLR_NO_FAST
-    (void)plan; return 0;
-#else
     if (!plan || plan->mode != CROSSCLR_MODE_BF16 || !plan->stash_bytes) return 0;
     if (plan->fast_path) return fast_stash_bytes_rect(plan->bpad, plan->Dpad, 1);
     return plan->Dpad > 1024 ? wide_stash_bytes_rect(plan->bpad, 1) : 0;      // wide plans: the generic second pass writes U AND Ut (below)
-#endif
 }
 // wide bf16 plans (Dpad > 1024) have no transposed launch of the saved backward: their second pass writes Ut behind U (like a remote block's)
 // and the backward is two DIRECT launches, over U with the rows' statistics and over Ut with the columns'
@@ -1017,29 +944,20 @@ extern "C" int crossclr_forward_save_s(const crossclr_plan* plan, const void* xh
                                        void* stream) {
     if (!plan || !xhat || !shift || !part || !stash || slot0 < 0) return fail(CROSSCLR_E_ARG, "NULL/negative argument");
     if (!stash_bytes_s(plan)) return fail(CROSSCLR_E_ARG, "this plan has no two-pass save-for-backward path (crossclr_stash_bytes_s == 0)");
-    const float *krows, *kcols;
-    if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
-    if (krows != kcols) return fail(CROSSCLR_E_ARG, "the local block's row and column negative scales are the same array");
+    const float* k;
     Geo g;
-    int rc = make_geo(plan, 1, plan->rank, -1, temperature, negative_weight, &g, true);
+    FwdSlot s;
+    int rc = local_save_args(plan, sw, temperature, negative_weight, true, part, slot0, &k, &g, &s);
     if (rc) return rc;
-    if (plan->fwd_slots <= 0 || slot0 % plan->fwd_slots != 0 || slot0 / plan->fwd_slots >= kLaunchGroups)
-        return fail(CROSSCLR_E_ARG, "slot0 must be L * plan->fwd_slots, L = 0..%d", kLaunchGroups - 1);
-    float* out = part + (size_t)slot0 * 2 * plan->bpad;
-    int* header = reinterpret_cast<int*>(part + ws_flag_off(plan)) + 4 * (slot0 / plan->fwd_slots);
-    if (plan->mode == CROSSCLR_MODE_BF16) {   // full (non-symmetric) second pass: bf16 records + the zero statistics behind them
-        rc = device_zero_header(header, stream);
-        if (rc) return rc;
+    const bool records = plan->mode == CROSSCLR_MODE_BF16;   // full (non-symmetric) second pass: bf16 records + the zero statistics behind them
+    if (!records && !env_knobs().disable_symmetric)
+        return fwd_sums(plan, g, saving(symmetric_pass(FwdPass::ShiftedSums, xhat, s, k, shift), stash), stream);
+    if ((rc = device_zero_header(s.header, stream))) return rc;
+    if (records) {
         rc = device_zero(static_cast<unsigned char*>(stash) + (wide_two_pass(plan) ? 2 : 1) * rect_bytes_s(plan), (size_t)2 * plan->bpad * 4, stream);
         if (rc) return rc;
-        return forward_generic(plan, g, xhat, xhat, out, kcols, shift, 2, stream, static_cast<float*>(stash), wide_two_pass(plan) ? shift : nullptr);
     }
-    if (!env_knobs().disable_symmetric)
-        return is_x3(plan) ? forward_generic_sym<x3_t>(plan, g, xhat, out, kcols, part + ws_colpart_off(plan), header, stream, static_cast<float*>(stash), shift)
-                           : forward_generic_sym<float>(plan, g, xhat, out, kcols, part + ws_colpart_off(plan), header, stream, static_cast<float*>(stash), shift);
-    rc = device_zero_header(header, stream);
-    if (rc) return rc;
-    return forward_generic(plan, g, xhat, xhat, out, kcols, shift, 2, stream, static_cast<float*>(stash));
+    return fwd_sums(plan, g, saving(full_pass(FwdPass::ShiftedSums, xhat, xhat, s.out, k, shift), stash, wide_two_pass(plan) ? shift : nullptr), stream);
 }
 
 extern "C" int crossclr_backward_saved_s(const crossclr_plan* plan, const void* xhat, const void* stash, float temperature,
@@ -1051,7 +969,6 @@ extern "C" int crossclr_backward_saved_s(const crossclr_plan* plan, const void* 
     Geo g;
     int rc = local_saved_args(plan, sw, temperature, negative_weight, true, &k, &g);
     if (rc) return rc;
-#ifndef CROSSCLR_NO_FAST
     if (plan->mode == CROSSCLR_MODE_BF16) {
         // W[p][q] = U[p][q] rz_p + U[q][p] rz_q as two 8 B^2 D launches of the saved backward (saved_two_pass) instead of the
         // 16 B^2 D (1 + ...) recompute of the generic kernel
@@ -1068,37 +985,29 @@ extern "C" int crossclr_backward_saved_s(const crossclr_plan* plan, const void* 
                               "fast_bwd_dsl_kernel (two-pass pair)", stream);
     }
     if (is_x3(plan)) return backward_saved_x3<true>(plan, g, xhat, stash, rz, wrz, k, gbuf, accumulate, stream);
-#endif
     return launch_saved32<true, false>(plan, g, xhat, stash, rz, wrz, kNoF, kNoF, k, kNoF, 2 * plan->bpad / 32, gbuf, accumulate, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
+// the generic gradient kernels' grid: 64-row blocks x DC-column chunks of D x plan->bwd_slices column slices
+static dim3 bwd_grid(const crossclr_plan* p, int DC) { return dim3(2 * p->bpad / 64, p->Dpad / DC, (unsigned)p->bwd_slices); }
 template <typename T>
 static int backward_generic(const crossclr_plan* p, const Geo& g, const void* rows, const void* cols,
                             const float* rz_rows, const float* wrz_rows, const float* rz_cols,
                             const float* wrz_cols, float* gbuf, int accumulate, const float* krows, const float* kcols,
                             const float* shift_rows, const float* shift_cols, void* stream) {
-    dim3 block(256);
-    const int rb = 2 * p->bpad / 64;
-    const bool skipping = g.skip_rank >= g.col_rank0 && g.skip_rank < g.col_rank0 + g.col_ranks;
-    const int ntiles = (g.col_ranks - (skipping ? 1 : 0)) * 2 * p->bpad / 64;   // usable column tiles
-    const int tps = (ntiles + p->bwd_slices - 1) / p->bwd_slices;
-    const unsigned nz = (unsigned)p->bwd_slices;
+    const int tps = (usable_col_ranks(g) * 2 * p->bpad / 64 + p->bwd_slices - 1) / p->bwd_slices;   // usable column tiles per slice
     // the generic backward slices D by DC and gbuf by plan->bwd_slices column slices; a plan made for the register-resident
     // kernels has the slice count of THEIR tiling, which is a valid (just not tuned) slice count here too
-#define CROSSCLR_LB2(DC, SW, RM) LAUNCH((bwd_kernel<T, DC, SW, RM>), dim3(rb, p->Dpad / DC, nz), block, stream, (const T*)rows, (const T*)cols, g, \
-                                        rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, tps, krows, kcols, shift_rows, shift_cols)
-#define CROSSCLR_LB(DC)                                          \
-    do {                                                          \
-        if (shift_rows) { if (krows) CROSSCLR_LB2(DC, true, true); else CROSSCLR_LB2(DC, false, true); }   \
-        else { if (krows) CROSSCLR_LB2(DC, true, false); else CROSSCLR_LB2(DC, false, false); }            \
-    } while (0)
-    if (p->Dpad % 512 == 0) CROSSCLR_LB(512);
-    else if (p->Dpad % 256 == 0) CROSSCLR_LB(256);
-    else if (p->Dpad % 128 == 0) CROSSCLR_LB(128);
-    else CROSSCLR_LB(64);
-#undef CROSSCLR_LB
-#undef CROSSCLR_LB2
+    with_d_chunk<512, 256, 128, 64>(p->Dpad, [&](auto dc) {
+        constexpr int DC = decltype(dc)::value;
+        auto launch = [&](auto sw, auto rm) {
+            LAUNCH((bwd_kernel<T, DC, decltype(sw)::value, decltype(rm)::value>), bwd_grid(p, DC), dim3(256), stream, (const T*)rows, (const T*)cols,
+                   g, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, tps, krows, kcols, shift_rows, shift_cols);
+        };
+        if (shift_rows) { if (krows) launch(std::true_type(), std::true_type()); else launch(std::false_type(), std::true_type()); }
+        else { if (krows) launch(std::true_type(), std::false_type()); else launch(std::false_type(), std::false_type()); }
+    });
     return launch_status(glabel<T>("bwd_kernel", "bwd_kernel<x3_t>"));
 }
 
@@ -1107,59 +1016,42 @@ extern "C" int crossclr_backward(const crossclr_plan* plan, const void* xhat_row
                                  float negative_weight, const float* rz_rows, const float* wrz_rows,
                                  const float* rz_cols, const float* wrz_cols, float* gbuf, int accumulate,
                                  void* stream) {
-    return crossclr_backward_w(plan, xhat_rows, xhat_cols, col_ranks, col_rank0, skip_rank, temperature, negative_weight,
-                               rz_rows, wrz_rows, rz_cols, wrz_cols, nullptr, gbuf, accumulate, stream);
+    return crossclr_backward_s(plan, xhat_rows, xhat_cols, col_ranks, col_rank0, skip_rank, temperature, negative_weight, rz_rows, wrz_rows,
+                               rz_cols, wrz_cols, nullptr, nullptr, nullptr, gbuf, accumulate, stream);
 }
-
 extern "C" int crossclr_backward_w(const crossclr_plan* plan, const void* xhat_rows, const void* xhat_cols,
                                    int col_ranks, int col_rank0, int skip_rank, float temperature,
                                    float negative_weight, const float* rz_rows, const float* wrz_rows,
                                    const float* rz_cols, const float* wrz_cols, const crossclr_sample_weights* sw,
                                    float* gbuf, int accumulate, void* stream) {
-    if (!plan || !xhat_rows || !xhat_cols || !rz_rows || !wrz_rows || !rz_cols || !wrz_cols || !gbuf)
-        return fail(CROSSCLR_E_ARG, "NULL argument");
-    const float *krows, *kcols;
-    if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
-    Geo g;
-    int rc = make_geo(plan, col_ranks, col_rank0, skip_rank, temperature, negative_weight, &g);
-    if (rc) return rc;
-#ifndef CROSSCLR_NO_FAST
-    if (plan->fast_bwd) {
-        rc = plan->fast_bwd == 2
-                 ? fast_backward16(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, stream)
-                 : fast_backward(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, stream);
-        return rc ? fail(rc, "fast backward: unsupported Dpad %d", plan->Dpad) : launch_status("fast_bwd_kernel");
-    }
-#endif
-    if (plan->mode == CROSSCLR_MODE_FP32)
-        return backward_generic<float>(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, nullptr, nullptr, stream);
-    if (is_x3(plan))
-        return backward_generic<x3_t>(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, nullptr, nullptr, stream);
-    return backward_generic<bf16_t>(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, nullptr, nullptr, stream);
+    return crossclr_backward_s(plan, xhat_rows, xhat_cols, col_ranks, col_rank0, skip_rank, temperature, negative_weight, rz_rows, wrz_rows,
+                               rz_cols, wrz_cols, sw, nullptr, nullptr, gbuf, accumulate, stream);
 }
-
+// no shifts: the single-pass soft-max (crossclr_backward_w); both: the two-pass one, on the generic kernel
 extern "C" int crossclr_backward_s(const crossclr_plan* plan, const void* xhat_rows, const void* xhat_cols, int col_ranks,
                                    int col_rank0, int skip_rank, float temperature, float negative_weight,
                                    const float* rz_rows, const float* wrz_rows, const float* rz_cols, const float* wrz_cols,
                                    const crossclr_sample_weights* sw, const float* shift_rows, const float* shift_cols,
                                    float* gbuf, int accumulate, void* stream) {
-    if (!shift_rows && !shift_cols)
-        return crossclr_backward_w(plan, xhat_rows, xhat_cols, col_ranks, col_rank0, skip_rank, temperature, negative_weight, rz_rows,
-                                   wrz_rows, rz_cols, wrz_cols, sw, gbuf, accumulate, stream);
-    if (!plan || !xhat_rows || !xhat_cols || !rz_rows || !wrz_rows || !rz_cols || !wrz_cols || !gbuf || !shift_rows || !shift_cols)
+    const bool two_pass = shift_rows || shift_cols;
+    if (!plan || !xhat_rows || !xhat_cols || !rz_rows || !wrz_rows || !rz_cols || !wrz_cols || !gbuf || (two_pass && (!shift_rows || !shift_cols)))
         return fail(CROSSCLR_E_ARG, "NULL argument");
     const float *krows, *kcols;
     if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
     Geo g;
-    int rc = make_geo(plan, col_ranks, col_rank0, skip_rank, temperature, negative_weight, &g, true);
+    int rc = make_geo(plan, col_ranks, col_rank0, skip_rank, temperature, negative_weight, &g, two_pass);
     if (rc) return rc;
-    if (plan->mode == CROSSCLR_MODE_FP32)
-        return backward_generic<float>(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, shift_rows, shift_cols, stream);
-    if (is_x3(plan))
-        return backward_generic<x3_t>(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, shift_rows, shift_cols, stream);
-    return backward_generic<bf16_t>(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, shift_rows, shift_cols, stream);
+    if (plan->fast_bwd && !two_pass) {
+        rc = plan->fast_bwd == 2
+                 ? fast_backward16(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, stream)
+                 : fast_backward(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate, krows, kcols, stream);
+        return rc ? fail(rc, "fast backward: unsupported Dpad %d", plan->Dpad) : launch_status("fast_bwd_kernel");
+    }
+    return with_plan_type(plan, [&](auto t) {
+        return backward_generic<typename decltype(t)::type>(plan, g, xhat_rows, xhat_cols, rz_rows, wrz_rows, rz_cols, wrz_cols, gbuf, accumulate,
+                                                            krows, kcols, shift_rows, shift_cols, stream);
+    });
 }
-
 
 // ---- rectangular blocks of the sharded step with saved exponentials ------------------------------------------------------
 // `first_rank`, `nranks`: column ranks first_rank .. first_rank+nranks-1 (mod plan->world) of the WHOLE gathered operand.
@@ -1177,9 +1069,6 @@ static int rect_geo(const crossclr_plan* plan, int first_rank, int nranks, float
 }
 
 extern "C" size_t crossclr_rect_stash_bytes(const crossclr_plan* plan, int nranks) {
-#ifdef CROSSCLR_NO_FAST
-    return 0;
-#else
     if (!plan || !plan->stash_bytes || nranks < 1) return 0;
     if (!plan->fast_path && plan->mode == CROSSCLR_MODE_FP32) {   // exact-fp32 plans: fp32 fragments of the rectangular block, up to 16 GiB
         const size_t sb = (size_t)(2 * plan->bpad / 32) * (size_t)(2 * plan->bpad / 32) * (size_t)nranks * 4096;
@@ -1189,7 +1078,6 @@ extern "C" size_t crossclr_rect_stash_bytes(const crossclr_plan* plan, int nrank
         return plan->operand_bytes * (size_t)plan->world < ((size_t)1 << 32) ? wide_stash_bytes_rect(plan->bpad, nranks) : 0;
     if (!plan->fast_path) return 0;
     return fast_stash_bytes_rect(plan->bpad, plan->Dpad, nranks);
-#endif
 }
 
 extern "C" int crossclr_forward_rect_save(const crossclr_plan* plan, const void* xhat_rows, const void* xhat_all, int first_rank,
@@ -1198,48 +1086,39 @@ extern "C" int crossclr_forward_rect_save(const crossclr_plan* plan, const void*
                                           void* stash, void* stream) {
     if (!plan || !xhat_rows || !xhat_all || !part || !stash || (with_colsums && !colsum_out)) return fail(CROSSCLR_E_ARG, "NULL argument");
     if (is_x3(plan)) return refuse_x3("crossclr_forward_rect_save");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "crossclr_forward_rect_save needs the register-resident path");
-#else
     if (plan->stash_bytes && !plan->fast_path && (plan->mode == CROSSCLR_MODE_FP32 || plan->Dpad > 1024)) {
         // exact-fp32 plans: the generic forward over the rank range, leaving its fp32 fragments behind ([row group][fragments of the range]);
         // wide bf16 plans (Dpad > 1024): the same launch leaves bf16 records ([row group][tile of the range]: fast_bwd_dsl_kernel<..., MODE 1>)
         if (with_colsums) return fail(CROSSCLR_E_ARG, "plans on the generic forward have no pair scheme (with_colsums must be 0)");
         if (!crossclr_rect_stash_bytes(plan, nranks)) return fail(CROSSCLR_E_ARG, "rectangular stash too large for this plan");
-        if (plan->fwd_slots <= 0 || slot0 < 0 || slot0 % plan->fwd_slots != 0 || slot0 / plan->fwd_slots >= kLaunchGroups)
-            return fail(CROSSCLR_E_ARG, "slot0 must be L * plan->fwd_slots, L = 0..%d", kLaunchGroups - 1);
+        FwdSlot s32;
+        if (int rs = fwd_slot(plan, part, slot0, &s32)) return rs;
         const float *kr32, *kc32;
         if (int rk = unpack_k(sw, &kr32, &kc32)) return rk;
         Geo g32;
         int rc32 = rect_geo(plan, first_rank, nranks, temperature, negative_weight, &g32);
         if (rc32) return rc32;
-        int* header32 = reinterpret_cast<int*>(part + ws_flag_off(plan)) + 4 * (slot0 / plan->fwd_slots);
-        rc32 = device_zero_header(header32, stream);
-        if (rc32) return rc32;
-        return forward_generic(plan, g32, xhat_rows, xhat_all, part + (size_t)slot0 * 2 * plan->bpad, kc32, nullptr, 0, stream, static_cast<float*>(stash));
+        if ((rc32 = device_zero_header(s32.header, stream))) return rc32;
+        return fwd_sums(plan, g32, saving(full_pass(FwdPass::Sums, xhat_rows, xhat_all, s32.out, kc32, nullptr), stash), stream);
     }
     if (!plan->stash_bytes || !plan->fast_path) return fail(CROSSCLR_E_ARG, "this plan has no save-for-backward path for remote blocks");
     if (with_colsums && nranks > (plan->world - 1) / 2) return fail(CROSSCLR_E_ARG, "a pair range holds at most (world-1)/2 ranks");
-    if (plan->fwd_slots <= 0 || slot0 < 0 || slot0 % plan->fwd_slots != 0 || slot0 / plan->fwd_slots >= kLaunchGroups)
-        return fail(CROSSCLR_E_ARG, "slot0 must be L * plan->fwd_slots, L = 0..%d", kLaunchGroups - 1);
+    FwdSlot s;
+    if (int rs = fwd_slot(plan, part, slot0, &s)) return rs;
     const float *krows, *kcols;
     if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
     Geo g;
     int rc = rect_geo(plan, first_rank, nranks, temperature, negative_weight, &g);
     if (rc) return rc;
-    float* out = part + (size_t)slot0 * 2 * plan->bpad;
-    int* header = reinterpret_cast<int*>(part + ws_flag_off(plan)) + 4 * (slot0 / plan->fwd_slots);
-    float* colpart = part + ws_paircol_off(plan);
     const FwdWork wk = fast_forward_work(plan, nranks, -1, false, with_colsums != 0);
-    rc = fast_forward_pipe(plan, g, wk, xhat_rows, xhat_all, out, colpart, header, with_colsums ? 3 : 2, krows, kcols, stash, stream);
+    rc = fast_forward_pipe(plan, g, wk, xhat_rows, xhat_all, s.out, s.paircol, s.header, with_colsums ? 3 : 2, krows, kcols, stash, stream);
     if (rc) return fail(rc, "fast_forward_pipe: unsupported Dpad %d", plan->Dpad);
     if (with_colsums) {
         const int nrb = 2 * plan->bpad / (32 * fast_fwd_tpr(plan->Dpad));
         const int ncols = nranks * 2 * plan->bpad;
-        LAUNCH(colsum_reduce_kernel, dim3((ncols + 255) / 256), dim3(256), stream, (const float*)colpart, nrb, ncols, colsum_out);
+        LAUNCH(colsum_reduce_kernel, dim3((ncols + 255) / 256), dim3(256), stream, (const float*)s.paircol, nrb, ncols, colsum_out);
     }
     return launch_status("fast_fwd_pipe_kernel (rect, save)");
-#endif
 }
 
 // what the saved backwards of a rectangular block share: the sample weights and the geometry of the rank range
@@ -1255,9 +1134,6 @@ extern "C" int crossclr_backward_rect_saved(const crossclr_plan* plan, const voi
                                             const crossclr_sample_weights* sw, float* gbuf, int accumulate, void* stream) {
     if (!plan || !xhat_all || !stash || !rz_rows || !wrz_rows || !rz_all || !wrz_all || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
     if (is_x3(plan)) return refuse_x3("crossclr_backward_rect_saved");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "crossclr_backward_rect_saved needs the register-resident path");
-#else
     const bool exact = plan->stash_bytes && !plan->fast_path && plan->mode == CROSSCLR_MODE_FP32;   // exact-fp32 plans: bwd_saved32_kernel<..., RECT>
     if (!exact && (!plan->stash_bytes || !(plan->fast_path || (plan->mode == CROSSCLR_MODE_BF16 && plan->Dpad > 1024))))
         return fail(CROSSCLR_E_ARG, "this plan has no save-for-backward path for remote blocks");
@@ -1271,7 +1147,6 @@ extern "C" int crossclr_backward_rect_saved(const crossclr_plan* plan, const voi
     rc = fast_backward_saved({SavedBlock::Rect, SavedOperand::RowMajor}, plan, g, xhat_all, stash, rz_rows, wrz_rows, rz_all, wrz_all, gbuf,
                              accumulate, krows, kcols, stream);
     return rc ? fail(rc, "fast_backward_saved: unsupported Dpad %d", plan->Dpad) : launch_status("fast_bwd_dsl_kernel (rect)");
-#endif
 }
 
 // ---- the two-pass regime's rectangular blocks (exact-fp32 plans): U and Ut of this rank's rows against other ranks' columns ----------
@@ -1294,22 +1169,19 @@ extern "C" int crossclr_forward_rect_save_s(const crossclr_plan* plan, const voi
     if (!plan || !xhat_rows || !xhat_all || !shift_rows || !shift_all || !part || !stash) return fail(CROSSCLR_E_ARG, "NULL argument");
     if (!crossclr_rect_stash_bytes_s(plan, nranks))
         return fail(CROSSCLR_E_ARG, "this plan has no two-pass save-for-backward path for remote blocks (crossclr_rect_stash_bytes_s == 0)");
-    if (plan->fwd_slots <= 0 || slot0 < 0 || slot0 % plan->fwd_slots != 0 || slot0 / plan->fwd_slots >= kLaunchGroups)
-        return fail(CROSSCLR_E_ARG, "slot0 must be L * plan->fwd_slots, L = 0..%d", kLaunchGroups - 1);
+    FwdSlot s;
+    if (int rs = fwd_slot(plan, part, slot0, &s)) return rs;
     const float *krows, *kcols;
     if (int rk = unpack_k(sw, &krows, &kcols)) return rk;
     Geo g;
     int rc = rect_geo(plan, first_rank, nranks, temperature, negative_weight, &g, true);
     if (rc) return rc;
-    int* header = reinterpret_cast<int*>(part + ws_flag_off(plan)) + 4 * (slot0 / plan->fwd_slots);
-    rc = device_zero_header(header, stream);
-    if (rc) return rc;
+    if ((rc = device_zero_header(s.header, stream))) return rc;
     if (plan->mode == CROSSCLR_MODE_BF16) {
         rc = device_zero(static_cast<unsigned char*>(stash) + 2 * crossclr_rect_stash_bytes(plan, nranks), rect_zero_floats(plan) * 4, stream);
         if (rc) return rc;
     }
-    return forward_generic(plan, g, xhat_rows, xhat_all, part + (size_t)slot0 * 2 * plan->bpad, kcols, shift_rows, 2, stream,
-                           static_cast<float*>(stash), shift_all);
+    return fwd_sums(plan, g, saving(full_pass(FwdPass::ShiftedSums, xhat_rows, xhat_all, s.out, kcols, shift_rows), stash, shift_all), stream);
 }
 
 extern "C" int crossclr_backward_rect_saved_s(const crossclr_plan* plan, const void* xhat_all, const void* stash, int first_rank,
@@ -1323,7 +1195,6 @@ extern "C" int crossclr_backward_rect_saved_s(const crossclr_plan* plan, const v
     Geo g;
     int rc = rect_saved_args(plan, sw, first_rank, nranks, temperature, negative_weight, true, &krows, &kcols, &g);
     if (rc) return rc;
-#ifndef CROSSCLR_NO_FAST
     if (plan->mode == CROSSCLR_MODE_BF16) {
         // W[p][q] = U[p][q] rz_p + Ut[p][q] rz_q: two rectangular launches of the saved backward (saved_two_pass), no recompute
         const size_t one = crossclr_rect_stash_bytes(plan, nranks);
@@ -1333,7 +1204,6 @@ extern "C" int crossclr_backward_rect_saved_s(const crossclr_plan* plan, const v
                               {SavedBlock::Rect, g, U + one, "two-pass, columns' side"}, zeros, rz_rows, wrz_rows, rz_all, wrz_all, krows, kcols,
                               gbuf, accumulate, "fast_bwd_dsl_kernel (rect, two-pass pair)", stream);
     }
-#endif
     return launch_saved32<true, true>(plan, g, xhat_all, stash, rz_rows, wrz_rows, rz_all, wrz_all, krows, kcols, nranks * (2 * plan->bpad / 32),
                                       gbuf, accumulate, stream);
 }
@@ -1343,16 +1213,12 @@ extern "C" int crossclr_backward_rect_saved_s(const crossclr_plan* plan, const v
 // kernel's rectangular launches read their column tiles from.
 extern "C" int crossclr_pack_xf_from_packed(const crossclr_plan* plan, const void* xhat_packed, int nranks, void* xhat_xf, void* stream) {
     if (!plan || !xhat_packed || !xhat_xf || nranks < 1) return fail(CROSSCLR_E_ARG, "bad arguments");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "crossclr_pack_xf_from_packed needs the register-resident path");
-#else
     if (!plan->xf_bytes) return fail(CROSSCLR_E_ARG, "this plan has no fragment-major operand (xf_bytes == 0)");
     const size_t tiles = (size_t)nranks * 2 * plan->bpad / 32;
     if (tiles > 0x7fffffffull) return fail(CROSSCLR_E_ARG, "too many rows");
     LAUNCH(xf_from_packed_kernel, dim3((unsigned)tiles, (unsigned)((plan->Dpad + 1023) / 1024)), dim3(256), stream, (const bf16_t*)xhat_packed,
            (unsigned char*)xhat_xf, plan->Dpad);
     return launch_status("xf_from_packed_kernel");
-#endif
 }
 
 // crossclr_backward_rect_saved on the fragment-major copy of the gathered operand, with the pair kernel (two tiles per barrier interval).
@@ -1361,9 +1227,6 @@ extern "C" int crossclr_backward_rect_saved_xfp(const crossclr_plan* plan, const
                                                 const float* wrz_rows, const float* rz_all, const float* wrz_all,
                                                 const crossclr_sample_weights* sw, float* gbuf, int accumulate, void* stream) {
     if (!plan || !xf_all || !stash || !rz_rows || !wrz_rows || !rz_all || !wrz_all || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "crossclr_backward_rect_saved_xfp needs the register-resident path");
-#else
     if (!plan->stash_bytes || !plan->fast_path || !plan->xf_bytes) return fail(CROSSCLR_E_ARG, "this plan has no fragment-major saved backward for remote blocks");
     if ((size_t)plan->world * plan->operand_bytes >= ((size_t)1 << 32) || fast_stash_bytes_rect(plan->bpad, plan->Dpad, nranks) >= ((size_t)1 << 32))
         return fail(CROSSCLR_E_ARG, "crossclr_backward_rect_saved_xfp uses 32-bit offsets (operand / stash of 4 GiB or more): use crossclr_backward_rect_saved");
@@ -1374,7 +1237,6 @@ extern "C" int crossclr_backward_rect_saved_xfp(const crossclr_plan* plan, const
     rc = fast_backward_saved({SavedBlock::Rect, SavedOperand::FragmentPair}, plan, g, xf_all, stash, rz_rows, wrz_rows, rz_all, wrz_all, gbuf,
                              accumulate, krows, kcols, stream);
     return rc ? fail(rc, "fast_backward_saved (xfp, rect): unsupported Dpad %d", plan->Dpad) : launch_status("fast_bwd_xfp_kernel (rect)");
-#endif
 }
 
 // The transpose of one saved rectangular block: what block (this rank x partner) contributes to the PARTNER's gradient buffer.
@@ -1385,9 +1247,6 @@ static int backward_rect_saved_t(const char* fn, SavedOperand operand, const cro
                                  const float* wrz_rows, const float* rz_all, const float* wrz_all, const crossclr_sample_weights* sw,
                                  float* gpartner, void* stream) {
     if (!plan || !x_rows || !stash || !rz_rows || !wrz_rows || !rz_all || !wrz_all || !gpartner) return fail(CROSSCLR_E_ARG, "NULL argument");
-#ifdef CROSSCLR_NO_FAST
-    return fail(CROSSCLR_E_ARG, "%s needs the register-resident path", fn);
-#else
     const bool pair = operand == SavedOperand::FragmentPair;
     if (!plan->stash_bytes || !plan->fast_path || (pair && !plan->xf_bytes))
         return fail(CROSSCLR_E_ARG, pair ? "this plan has no fragment-major saved backward for remote blocks"
@@ -1407,7 +1266,6 @@ static int backward_rect_saved_t(const char* fn, SavedOperand operand, const cro
                              kcols ? kcols + partner * n2 : nullptr, krows, stream);
     if (rc) return fail(rc, "fast_backward_saved%s: unsupported Dpad %d", pair ? " (xfp, transposed)" : "", plan->Dpad);
     return launch_status(pair ? "fast_bwd_xfp_kernel (rect, transposed)" : "fast_bwd_dsl_kernel (rect, transposed)");
-#endif
 }
 extern "C" int crossclr_backward_rect_saved_t_xfp(const crossclr_plan* plan, const void* xf_rows, const void* stash, int first_rank,
                                                   int nranks, int which, float temperature, float negative_weight, const float* rz_rows,
@@ -1436,17 +1294,16 @@ extern "C" int crossclr_backward_ranks(const crossclr_plan* plan, const void* xh
     Geo g;
     int rc = rect_geo(plan, first_rank, nranks, temperature, negative_weight, &g);
     if (rc) return rc;
-#ifndef CROSSCLR_NO_FAST
     if (plan->fast_bwd) {
         rc = plan->fast_bwd == 2
                  ? fast_backward16(plan, g, xhat_rows, xhat_all, rz_rows, wrz_rows, rz_all, wrz_all, gbuf, accumulate, krows, kcols, stream)
                  : fast_backward(plan, g, xhat_rows, xhat_all, rz_rows, wrz_rows, rz_all, wrz_all, gbuf, accumulate, krows, kcols, stream);
         return rc ? fail(rc, "fast backward: unsupported Dpad %d", plan->Dpad) : launch_status("fast_bwd_kernel (ranks)");
     }
-#endif
-    if (plan->mode == CROSSCLR_MODE_FP32)
-        return backward_generic<float>(plan, g, xhat_rows, xhat_all, rz_rows, wrz_rows, rz_all, wrz_all, gbuf, accumulate, krows, kcols, nullptr, nullptr, stream);
-    return backward_generic<bf16_t>(plan, g, xhat_rows, xhat_all, rz_rows, wrz_rows, rz_all, wrz_all, gbuf, accumulate, krows, kcols, nullptr, nullptr, stream);
+    return with_plan_type<false>(plan, [&](auto t) {
+        return backward_generic<typename decltype(t)::type>(plan, g, xhat_rows, xhat_all, rz_rows, wrz_rows, rz_all, wrz_all, gbuf, accumulate, krows,
+                                                            kcols, nullptr, nullptr, stream);
+    });
 }
 
 template <typename TIN>
@@ -1523,36 +1380,35 @@ static int score_geo(const crossclr_plan* p, float margin, Geo* g) {
     g->c_inter = 1.f; g->c_intra = 1.f; g->m2 = margin;
     return CROSSCLR_OK;
 }
-template <typename T>
-static void score_launch(const crossclr_plan* plan, const Geo& g, const void* x, float* out, float* cnt, const float* diag, int mode,
-                         void* stream, float* colpart = nullptr, unsigned char* hinge_mask = nullptr) {
-    if (mode == 3 && colpart) {   // one pass: rows of modality 0 against the column tiles of modality 1, column statistics for the rest
-        const int half_tiles = plan->bpad / 128, nsplit = plan->fwd_slots;
-        const int tps = (half_tiles + nsplit - 1) / nsplit;
-        // (the kernel's `header` argument is free in this mode: it carries the optional hinge mask of crossclr_score_rows_save)
-        LAUNCH((fwd_sums_kernel<T, false, 3, false, true>), dim3(plan->bpad / 128, nsplit), dim3(256), stream, (const T*)x, (const T*)x, g, tps, out,
-               (const float*)nullptr, diag, cnt, reinterpret_cast<int*>(hinge_mask), colpart);
-        return;
-    }
-    const int ntiles = 2 * plan->bpad / 128;
-    const int nsplit = mode == 4 ? 1 : plan->fwd_slots;
-    const int tps = (ntiles + nsplit - 1) / nsplit;
-    dim3 grid(2 * plan->bpad / 128, nsplit), block(256);
-    if (mode == 4) LAUNCH((fwd_sums_kernel<T, false, 4>), grid, block, stream, (const T*)x, (const T*)x, g, tps, out, (const float*)nullptr, diag, cnt, (int*)nullptr, (float*)nullptr);
-    else LAUNCH((fwd_sums_kernel<T, false, 3>), grid, block, stream, (const T*)x, (const T*)x, g, tps, out, (const float*)nullptr, diag, cnt, (int*)nullptr, (float*)nullptr);
-}
-
 extern "C" int crossclr_score_diag(const crossclr_plan* plan, const void* xhat, float* diag, void* stream) {
     if (!plan || !xhat || !diag) return fail(CROSSCLR_E_ARG, "NULL argument");
     Geo g;
     if (int rc = score_geo(plan, 0.f, &g)) return rc;
-    if (plan->mode == CROSSCLR_MODE_FP32) score_launch<float>(plan, g, xhat, diag, nullptr, nullptr, 4, stream);
-    else score_launch<bf16_t>(plan, g, xhat, diag, nullptr, nullptr, 4, stream);
-    return launch_status("fwd_sums_kernel (positive-pair scores)");
+    const FwdSums d = full_pass(FwdPass::ScoreDiag, xhat, xhat, diag, nullptr, nullptr);
+    return with_plan_type<false>(plan, [&](auto t) { return launch_fwd_sums<typename decltype(t)::type>(plan, g, d, stream); });
 }
 
 static int score_rows_impl(const crossclr_plan* plan, const void* xhat, const float* diag, float margin, float* part,
-                           float* hinge, float* active, double* loss_sum, unsigned char* hinge_mask, void* stream);
+                           float* hinge, float* active, double* loss_sum, unsigned char* hinge_mask, void* stream) {
+    if (!plan || !xhat || !diag || !part || !hinge || !active || !loss_sum) return fail(CROSSCLR_E_ARG, "NULL argument");
+    Geo g;
+    if (int rc = score_geo(plan, margin, &g)) return rc;
+    if (plan->fwd_slots <= 0) return fail(CROSSCLR_E_ARG, "bad plan");
+    float* cnt = part + (size_t)plan->fwd_slots * 2 * plan->bpad;     // launch group 1 of the forward workspace
+    float* colpart = env_knobs().disable_symmetric ? nullptr : part + ws_colpart_off(plan);   // one pass for both directions
+    // colpart: rows of modality 0 against the column tiles of modality 1, column statistics for the rest (the kernel's `header` argument is
+    // free in this mode: it carries the optional hinge mask of crossclr_score_rows_save); else every row against every column tile
+    FwdSums d = full_pass(FwdPass::ScoreRows, xhat, xhat, part, nullptr, diag);
+    d.stash = cnt;
+    if (colpart) { d.symmetric = true; d.header = reinterpret_cast<int*>(hinge_mask); d.colpart = colpart; }
+    if (int rc = with_plan_type<false>(plan, [&](auto t) { return launch_fwd_sums<typename decltype(t)::type>(plan, g, d, stream); })) return rc;
+    const int nb = plan->loss_ws_doubles - 1;
+    LAUNCH(score_finish_kernel, dim3(nb), dim3(256), stream, (const float*)part, (const float*)cnt, plan->fwd_slots, plan->bpad, plan->b,
+           hinge, active, loss_sum, (const float*)colpart);
+    // loss_sum[0] = sum of the hinges, loss_sum[1] = the reference's mean: / (B * B)   (trainer/loss.py:41)
+    LAUNCH(fwd_finish_reduce_kernel, dim3(1), dim3(64), stream, loss_sum, nb, 1.0 / ((double)plan->b * (double)plan->b));
+    return launch_status("score_finish_kernel");
+}
 extern "C" int crossclr_score_rows(const crossclr_plan* plan, const void* xhat, const float* diag, float margin, float* part,
                                    float* hinge, float* active, double* loss_sum, void* stream) {
     return score_rows_impl(plan, xhat, diag, margin, part, hinge, active, loss_sum, nullptr, stream);
@@ -1567,37 +1423,15 @@ extern "C" int crossclr_score_rows_save(const crossclr_plan* plan, const void* x
     if (env_knobs().disable_symmetric) return fail(CROSSCLR_E_ARG, "CROSSCLR_DISABLE_SYMMETRIC: the hinge mask is written by the one-pass evaluation only");
     return score_rows_impl(plan, xhat, diag, margin, part, hinge, active, loss_sum, static_cast<unsigned char*>(hinge_mask), stream);
 }
-static int score_rows_impl(const crossclr_plan* plan, const void* xhat, const float* diag, float margin, float* part,
-                           float* hinge, float* active, double* loss_sum, unsigned char* hinge_mask, void* stream) {
-    if (!plan || !xhat || !diag || !part || !hinge || !active || !loss_sum) return fail(CROSSCLR_E_ARG, "NULL argument");
-    Geo g;
-    if (int rc = score_geo(plan, margin, &g)) return rc;
-    if (plan->fwd_slots <= 0) return fail(CROSSCLR_E_ARG, "bad plan");
-    float* cnt = part + (size_t)plan->fwd_slots * 2 * plan->bpad;     // launch group 1 of the forward workspace
-    float* colpart = env_knobs().disable_symmetric ? nullptr : part + ws_colpart_off(plan);   // one pass for both directions
-    if (plan->mode == CROSSCLR_MODE_FP32) score_launch<float>(plan, g, xhat, part, cnt, diag, 3, stream, colpart, hinge_mask);
-    else score_launch<bf16_t>(plan, g, xhat, part, cnt, diag, 3, stream, colpart, hinge_mask);
-    if (int rc = launch_status("fwd_sums_kernel (score rows)")) return rc;
-    const int nb = plan->loss_ws_doubles - 1;
-    LAUNCH(score_finish_kernel, dim3(nb), dim3(256), stream, (const float*)part, (const float*)cnt, plan->fwd_slots, plan->bpad, plan->b,
-           hinge, active, loss_sum, (const float*)colpart);
-    // loss_sum[0] = sum of the hinges, loss_sum[1] = the reference's mean: / (B * B)   (trainer/loss.py:41)
-    LAUNCH(fwd_finish_reduce_kernel, dim3(1), dim3(64), stream, loss_sum, nb, 1.0 / ((double)plan->b * (double)plan->b));
-    return launch_status("score_finish_kernel");
-}
 
 template <typename T>
 static int maxmargin_backward_t(const crossclr_plan* p, const Geo& g, const void* x, const float* diag, float* gbuf, void* stream) {
-    dim3 block(256);
-    const unsigned rb = 2 * p->bpad / 64, nz = (unsigned)p->bwd_slices;
-    const int ntiles = 2 * p->bpad / 64;
-    const int tps = (ntiles + p->bwd_slices - 1) / p->bwd_slices;
-#define CROSSCLR_LMM(DC) LAUNCH((bwd_kernel<T, DC, false, false, 1>), dim3(rb, p->Dpad / DC, nz), block, stream, (const T*)x, (const T*)x, g, \
-                                diag, diag, diag, diag, gbuf, 0, tps, (const float*)nullptr, (const float*)nullptr, diag, diag)
-    if (p->Dpad % 256 == 0) CROSSCLR_LMM(256);
-    else if (p->Dpad % 128 == 0) CROSSCLR_LMM(128);
-    else CROSSCLR_LMM(64);
-#undef CROSSCLR_LMM
+    const int tps = (2 * p->bpad / 64 + p->bwd_slices - 1) / p->bwd_slices;
+    with_d_chunk<256, 128, 64>(p->Dpad, [&](auto dc) {
+        constexpr int DC = decltype(dc)::value;
+        LAUNCH((bwd_kernel<T, DC, false, false, 1>), bwd_grid(p, DC), dim3(256), stream, (const T*)x, (const T*)x, g, diag, diag, diag, diag, gbuf,
+               0, tps, kNoF, kNoF, diag, diag);
+    });
     return launch_status("bwd_kernel (max-margin)");
 }
 
@@ -1606,29 +1440,25 @@ extern "C" int crossclr_maxmargin_backward(const crossclr_plan* plan, const void
     if (!plan || !xhat || !diag || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
     Geo g;
     if (int rc = score_geo(plan, margin, &g)) return rc;
-    if (plan->mode == CROSSCLR_MODE_FP32) return maxmargin_backward_t<float>(plan, g, xhat, diag, gbuf, stream);
-    return maxmargin_backward_t<bf16_t>(plan, g, xhat, diag, gbuf, stream);
+    return with_plan_type<false>(plan, [&](auto t) { return maxmargin_backward_t<typename decltype(t)::type>(plan, g, xhat, diag, gbuf, stream); });
 }
 
 template <typename T>
 static int maxmargin_backward_saved_t(const crossclr_plan* p, const Geo& g, const void* x, const unsigned char* mask, float* gbuf, void* stream) {
-    dim3 block(256);
-    const unsigned rb = 2 * p->bpad / 64, nz = (unsigned)p->bwd_slices;
-    const int ntiles = 2 * p->bpad / 64;
-    const int tps = (ntiles + p->bwd_slices - 1) / p->bwd_slices;
-#define CROSSCLR_LMS(DC) LAUNCH((maxmargin_saved_kernel<T, DC>), dim3(rb, p->Dpad / DC, nz), block, stream, (const T*)x, g, mask, gbuf, tps)
-    if (p->Dpad % 256 == 0) CROSSCLR_LMS(256);
-    else if (p->Dpad % 128 == 0) CROSSCLR_LMS(128);
-    else CROSSCLR_LMS(64);
-#undef CROSSCLR_LMS
+    const int tps = (2 * p->bpad / 64 + p->bwd_slices - 1) / p->bwd_slices;
+    with_d_chunk<256, 128, 64>(p->Dpad, [&](auto dc) {
+        constexpr int DC = decltype(dc)::value;
+        LAUNCH((maxmargin_saved_kernel<T, DC>), bwd_grid(p, DC), dim3(256), stream, (const T*)x, g, mask, gbuf, tps);
+    });
     return launch_status("maxmargin_saved_kernel");
 }
 extern "C" int crossclr_maxmargin_backward_saved(const crossclr_plan* plan, const void* xhat, const void* hinge_mask, float* gbuf, void* stream) {
     if (!plan || !xhat || !hinge_mask || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
     Geo g;
     if (int rc = score_geo(plan, 0.f, &g)) return rc;
-    if (plan->mode == CROSSCLR_MODE_FP32) return maxmargin_backward_saved_t<float>(plan, g, xhat, static_cast<const unsigned char*>(hinge_mask), gbuf, stream);
-    return maxmargin_backward_saved_t<bf16_t>(plan, g, xhat, static_cast<const unsigned char*>(hinge_mask), gbuf, stream);
+    return with_plan_type<false>(plan, [&](auto t) {
+        return maxmargin_backward_saved_t<typename decltype(t)::type>(plan, g, xhat, static_cast<const unsigned char*>(hinge_mask), gbuf, stream);
+    });
 }
 
 extern "C" int crossclr_maxmargin_backward_finish(const crossclr_plan* plan, const float* gbuf, const void* im, const void* s,

@@ -57,6 +57,10 @@ struct Geo {
     int row_shift;  // 1: max |logit| is beyond any fixed shift in fp32 (temperature < ~0.008): the generic kernels take a per-row
                     // shift (the row maximum, found by a first pass) like the reference's float64 soft-max does (loss.py:60)
 };
+// host side: the column ranks a launch evaluates (col_ranks less the skipped one, if that lies in the range); <= 0: nothing to do
+inline int usable_col_ranks(const Geo& g) {
+    return g.col_ranks - (g.skip_rank >= g.col_rank0 && g.skip_rank < g.col_rank0 + g.col_ranks ? 1 : 0);
+}
 
 // ---------------------------------------------------------------------------------------------
 // portability layer: the handful of gfx950 builtins the kernels use

@@ -912,8 +912,7 @@ CROSSCLR_LEAF int fast_forward_pipe(const crossclr_plan* p, const Geo& g, const 
 static inline int fast_forward(const crossclr_plan* p, const Geo& g, const void* rows, const void* cols, float* part,
                                float* colpart, int* header, bool symmetric, const float* krows, const float* kcols,
                                void* stream, bool pairs = false) {
-    const bool skipping = g.skip_rank >= g.col_rank0 && g.skip_rank < g.col_rank0 + g.col_ranks;
-    const FwdWork wk = fast_forward_work(p, g.col_ranks, skipping ? g.skip_rank : -1, symmetric, pairs);
+    const FwdWork wk = fast_forward_work(p, g.col_ranks, usable_col_ranks(g) < g.col_ranks ? g.skip_rank : -1, symmetric, pairs);
     if (wk.total <= 0) return CROSSCLR_OK;
     const bf16_t* r = (const bf16_t*)rows;
     const bf16_t* c = (const bf16_t*)cols;
@@ -1093,9 +1092,8 @@ static inline int fast_backward_saved(SavedKind kind, const crossclr_plan* p, co
                                       const float* wrz, const float* rz_cols, const float* wrz_cols, float* gbuf, int accumulate,
                                       const float* ks, const float* kc, void* stream) {
     const bool rect = kind.block == SavedBlock::Rect;
-    const bool skipping = rect && g.col_wrap == 0 && g.skip_rank >= g.col_rank0 && g.skip_rank < g.col_rank0 + g.col_ranks;
     const int per_rank = 2 * p->bpad / 32;
-    const int ntiles = (rect ? g.col_ranks - (skipping ? 1 : 0) : 1) * per_rank;
+    const int ntiles = (rect ? (g.col_wrap == 0 ? usable_col_ranks(g) : g.col_ranks) : 1) * per_rank;
     if (ntiles <= 0) return CROSSCLR_OK;
     const int tps = ((ntiles + p->bwd_slices - 1) / p->bwd_slices + 1) & ~1;
     SavedLaunch a = {p, g, cols, stash, rz, wrz, rz_cols, wrz_cols, gbuf, accumulate, ks, kc, kind, tps, stream, 0};
@@ -1128,8 +1126,7 @@ CROSSCLR_LEAF int fast_backward16(const crossclr_plan* p, const Geo& g, const vo
                                   const float* kcols, void* stream) {
     note_kernel(1, "fast_bwd16_kernel (recomputing)");
     const bool sw = krows != nullptr && kcols != nullptr;
-    const bool skipping = g.skip_rank >= g.col_rank0 && g.skip_rank < g.col_rank0 + g.col_ranks;
-    const int ntiles = (g.col_ranks - (skipping ? 1 : 0)) * 2 * p->bpad / 32;   // usable column tiles
+    const int ntiles = usable_col_ranks(g) * 2 * p->bpad / 32;   // usable column tiles
     const int tps = (ntiles + p->bwd_slices - 1) / p->bwd_slices;
     const bf16_t* r = (const bf16_t*)rows;
     const bf16_t* c = (const bf16_t*)cols;
@@ -1161,8 +1158,7 @@ CROSSCLR_LEAF int fast_backward(const crossclr_plan* p, const Geo& g, const void
                                 const float* kcols, void* stream) {
     note_kernel(1, "fast_bwd_kernel (recomputing)");
     const bool sw = krows != nullptr && kcols != nullptr;
-    const bool skipping = g.skip_rank >= g.col_rank0 && g.skip_rank < g.col_rank0 + g.col_ranks;
-    const int ntiles = (g.col_ranks - (skipping ? 1 : 0)) * 2 * p->bpad / 32;   // usable column tiles
+    const int ntiles = usable_col_ranks(g) * 2 * p->bpad / 32;   // usable column tiles
     const int tps = (ntiles + p->bwd_slices - 1) / p->bwd_slices;
     dim3 grid(2 * p->bpad / 128, p->bwd_slices), block(256);
     const bf16_t* r = (const bf16_t*)rows;

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import crossclr_amd
+import fwd_sums_table as fst
 from conftest import golden_arrays, golden_index, golden_inputs
 from crossclr_amd import _native as nat
 from crossclr_amd import loss as L
@@ -820,3 +821,12 @@ def test_second_order_terms_on_the_device():
     ((rv.double() ** 2).sum() + (rt.double() ** 2).sum()).backward()
     assert (vd.grad.cpu() - vc.grad).abs().max().item() <= 1e-4 * vc.grad.abs().max().item()
     assert (td.grad.cpu() - tc.grad).abs().max().item() <= 1e-4 * tc.grad.abs().max().item()
+
+
+@pytest.mark.parametrize("B,D", fst.SHAPES)
+@pytest.mark.parametrize("row", [r for r in fst.ROWS if r.knob is None], ids=fst.row_id)
+def test_fwd_sums_launches_through_the_c_abi(row, B, D):
+    """The table of tests/test_kernels_emulated.py::test_fwd_sums_launches_through_the_c_abi on the hipcc build (the rows no environment
+    knob is needed for: this library reads its knobs once per process): the launcher's template choice, seen as the launch's name and
+    the loss it leads to."""
+    fst.check_row(row, B, D, torch.device("cuda"))

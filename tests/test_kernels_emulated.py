@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import crossclr_amd
+import fwd_sums_table as fst
 from conftest import golden_arrays, golden_index, golden_inputs
 from crossclr_amd import _native as nat
 from oracle import crossclr_oracle as orc
@@ -703,3 +704,14 @@ def test_pair_scheme_saved_blocks_through_the_c_abi(weighted):
     scale = vg.grad.abs().max().item()
     assert (gv - vg.grad).abs().max().item() <= 3e-3 * scale      # bf16 weights rounded in different tile groupings
     assert (gt - tg.grad).abs().max().item() <= 3e-3 * scale
+
+
+@pytest.mark.parametrize("B,D", fst.SHAPES)
+@pytest.mark.parametrize("row", fst.ROWS, ids=fst.row_id)
+def test_fwd_sums_launches_through_the_c_abi(row, B, D, monkeypatch):
+    """Every (operand type x weighted x pass x save x symmetric) instantiation of fwd_sums_kernel the C ABI reaches at these widths: the
+    entry point that reaches it names exactly that launch in crossclr_last_kernel(0), and the forward it belongs to gives the oracle's
+    loss (tests/fwd_sums_table.py: the table, the entry points and the bars)."""
+    if row.knob:
+        monkeypatch.setenv(row.knob, "1")
+    fst.check_row(row, B, D, torch.device("cpu"))
