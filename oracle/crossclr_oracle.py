@@ -298,3 +298,184 @@ def make_inputs(kind: str, B: int, D: int, seed: int, dtype: torch.dtype = torch
     else:
         raise ValueError(kind)
     return v.to(dtype), t.to(dtype)
+
+
+# --------------------------------------------------------------------------- #
+# (d) dense stacked weight model: the gradient product G = W X of the kernels  #
+# --------------------------------------------------------------------------- #
+LOG2E = 1.4426950408889634
+
+
+def _f32(x: torch.Tensor) -> torch.Tensor:
+    """round a float64 tensor to float32 and widen it again"""
+    return x.float().double()
+
+
+def _bf16(x: torch.Tensor) -> torch.Tensor:
+    """float64 -> float32 -> bf16 (round to nearest even, as the kernels' conversion does) -> float64"""
+    return x.float().bfloat16().double()
+
+
+def _near_bf16_tie(x: torch.Tensor, ulps: int = 8) -> torch.Tensor:
+    """where the fp32 value of x lies within `ulps` fp32 units of the midpoint of two neighbouring bf16 values"""
+    low = x.float().contiguous().view(torch.int32) & 0xFFFF
+    return (low - 0x8000).abs() <= ulps
+
+
+_F32_LOG2E = float(torch.tensor(LOG2E).float())            # kLog2e, kLn2 of crossclr_device.h: float constants
+_F32_LN2 = float(torch.tensor(0.6931471805599453).float())
+
+
+def _kernel_scales(temperature: float, negative_weight: float) -> Tuple[float, float, float]:
+    """(c_inter, c_intra, ln 2) as make_geo (crossclr_api.cpp) forms them: logit in log2 units = cos * c, from the float temperature and
+    negative weight of the C-ABI and the float constant log2(e), rounded to fp32; back to natural units with the float constant ln 2"""
+    it = 1.0 / float(torch.tensor(float(temperature)).float())
+    w32 = float(torch.tensor(float(negative_weight)).float())
+    return float(torch.tensor(it * _F32_LOG2E).float()), float(torch.tensor(it * w32 * _F32_LOG2E).float()), _F32_LN2
+
+
+def _kernel_common_shift(temperature: float, negative_weight: float) -> float:
+    """m2 of make_geo: the common soft-max shift max(0, max(1, |w|) / tau - 64) in log2 units, as a float (single-pass regime)"""
+    bound = max(1.0, abs(float(torch.tensor(float(negative_weight)).float()))) / float(torch.tensor(float(temperature)).float())
+    return float(torch.tensor((bound - 64.0 if bound > 64.0 else 0.0) * _F32_LOG2E).float())
+
+
+def needs_row_shift(temperature: float, negative_weight: float) -> bool:
+    """the two-pass soft-max regime of the kernels: max |logit| = max(1, |w|) / tau above 128"""
+    return max(1.0, abs(float(negative_weight))) / float(temperature) > 128.0
+
+
+def stacked_weight_model(video, text, temperature=0.03, negative_weight=0.8, k=None, omega=None, roundings: int = 0,
+                         fp32_logits=False) -> Dict[str, torch.Tensor]:
+    """Dense float64 form of what every backward kernel multiplies: the stacked unit rows X = [vhat; that] ([2B, D]) and the
+    weight matrix W ([2B, 2B]) with
+
+        inter-modal blocks   W_pq = E_pq (o_p / Z_p + o_q / Z_q)
+        intra-modal blocks   W_pq = w E_pq (o_p k_q / Z_p + o_q k_p / Z_q),   W_pp = 0
+
+    (k = (k_video, k_text) negative scales, omega = (o_video, o_text) loss weights; None = ones), so that
+    d loss / d xhat = (W X) / (2 B tau) - the positive-pair term (`grads_from_stacked_weights`).
+
+    roundings = 0  the exact closed form (the yardstick of the fp32 and bf16x3 modes).  fp32_logits = "scale" evaluates it with the scales
+                   the kernels hold (`_kernel_scales`: the C-ABI takes the temperature as a float -- float(0.004) is 4.7e-8 above
+                   0.004, 1.1e-5 of a logit of 235 --, log2(e) and ln 2 are float constants, the scale is rounded to fp32), "product"
+                   also rounds every scaled logit to fp32: the two-pass regime's forward yardstick, where logZ ~ 1 / tau = 250.
+    roundings = 2  the bf16 SAVED backward (crossclr_kernels_dsl.h:3, crossclr_kernels_dslp.h): the forward leaves
+                   E = bf16(exp2(x - m2)) behind, x = fp32(cos * fp32(log2(e) / tau [* w])) and m2 the common shift
+                   max(0, max(1, |w|) / tau - 64) log2(e); the backward forms bf16(fp32(E * fp32(rz_p + rz_q))) with rz = fp32(o / Z),
+                   wrz = fp32(fp32(w) rz) on the intra-modal blocks (sample weights: fp32(fma(rz_p, k_q, rz_q k_p))), Z from the
+                   UNROUNDED exponentials.  Two bf16 roundings per weight; the product with X and the normalise-backward are exact.
+    roundings = 1  the bf16 RECOMPUTING backward (fast_bwd_kernel / fast_bwd16_kernel, crossclr_kernels_fast.h): the same
+                   expression from the fp32 exponential: one bf16 rounding per weight.
+    The rounded forms mirror the kernels' fp32 operations, so a weight falls on the other side of a bf16 tie only where the
+    hardware's exp2 does (`slack_rows`: what that may move a row's gradient by).
+    Two-pass regime (max(1, |w|) / tau > 128), roundings = 2 (crossclr_backward_saved_s, crossclr_api.cpp): the second pass of the
+    forward leaves U[p][q] = bf16(exp2(fma(cos, c, -shift_p))) behind, shift_p = the row maximum of fp32(cos c) over the unmasked
+    columns; the backward is two launches of the saved kernel, direct and transposed, each rounding its own weight:
+    W_pq = bf16(fp32(U[p][q] fp32(rz_p k_q))) + bf16(fp32(U[q][p] fp32(rz_q k_p))), rz = fp32(o / sum_q exp2(x - shift_p)).
+    The dict also carries the pieces (`logits`, `k_cols`, `k_rows`, `intra`, `w`) from which `exact_weights` forms W, for tests that
+    perturb a statistic."""
+    B = video.shape[0]
+    vhat, vnorm = _unit_rows(video)
+    that, tnorm = _unit_rows(text)
+    X = torch.cat([vhat, that], 0)
+    n = 2 * B
+    it, w = 1.0 / float(temperature), float(negative_weight)
+    two_pass = needs_row_shift(temperature, negative_weight)
+    if roundings == 1 and two_pass:
+        raise NotImplementedError("the one-rounding model covers the single-pass regime (the two-pass bf16 step saves)")
+    ones = torch.ones(B, dtype=torch.float64)
+    kk = torch.cat([x.double() for x in (k if k is not None else (ones, ones))])
+    om = torch.cat([x.double() for x in (omega if omega is not None else (ones, ones))])
+    mod = torch.arange(n) >= B
+    intra = mod[:, None] == mod[None, :]
+    eye = torch.eye(n, dtype=torch.bool)
+    f64 = lambda a, b: torch.where(intra, torch.tensor(a, dtype=torch.float64), torch.tensor(b, dtype=torch.float64))
+    S = X @ X.t()
+    c_inter, c_intra, ln2 = _kernel_scales(temperature, negative_weight)
+    kq = torch.where(intra, kk[None, :], torch.ones(n, n, dtype=torch.float64))      # the column's negative scale (intra-modal blocks)
+    kr = torch.where(intra, kk[:, None], torch.ones(n, n, dtype=torch.float64))      # the row's
+    slack = torch.zeros(n, dtype=torch.float64)
+    logits = None
+    if not roundings:
+        logits = S * f64(it * w, it)
+        if fp32_logits:
+            x2 = S * f64(c_intra, c_inter)
+            logits = (_f32(x2) if fp32_logits == "product" else x2) * ln2
+        logits[eye] = 0.0
+        lk = torch.where(kk > 0, torch.log(kk.clamp_min(1e-300)), torch.full_like(kk, float("-inf")))
+        logZ = torch.logsumexp(logits + torch.where(intra, lk[None, :], torch.zeros_like(logits)), 1)
+        W = exact_weights(logits, logZ, logZ, om, om, kq, kr, intra, w)
+    else:
+        if two_pass:
+            # pass 1: the row maximum of the rounded scaled logits over the unmasked columns; pass 2: exp2(fma(cos, c, -shift_p))
+            xs = _f32(_f32(S) * f64(c_intra, c_inter))
+            live = ~eye & (~intra | (kk[None, :] > 0))
+            shift = torch.where(live, xs, torch.full_like(xs, float("-inf"))).amax(1)
+        else:
+            shift = torch.full((n,), _kernel_common_shift(temperature, negative_weight), dtype=torch.float64)
+        x2 = _f32(_f32(S) * f64(c_intra, c_inter) - shift[:, None])
+        x2[eye] = -shift                                # the masked self pair: logit 0
+        E = _f32(torch.exp2(x2))
+        Zs = (E * kq).sum(1)
+        logZ = shift * ln2 + torch.log(Zs)
+        rz = _f32(om / Zs)
+        wrz = _f32(float(torch.tensor(w).float()) * rz)
+        U = _bf16(E) if roundings == 2 else E
+        rs = torch.where(intra, wrz[:, None], rz[:, None]).expand(n, n)
+        cs = torch.where(intra, wrz[None, :], rz[None, :]).expand(n, n)
+        # What this model lacks: the last place of the hardware's exp2 (accurate to a unit of fp32, not correctly rounded).  A weight whose
+        # fp32 value -- or whose saved exponential's -- lies within 8 fp32 units of a bf16 rounding boundary may fall on either side of it on
+        # the device: such a weight (about one in 4000) is allowed two bf16 steps, and its row the resulting `slack_rows`.
+        tie_e = _near_bf16_tie(E) if roundings == 2 else torch.zeros_like(eye)
+        if two_pass:
+            # two launches, each weight rounded on its own: bf16(U[p][q] rz_p k_q) + bf16(U[q][p] rz_q k_p)
+            pre1, pre2 = _f32(U * _f32(rs * kq)), _f32(U.t() * _f32(cs * kr))
+            W = _bf16(pre1) + _bf16(pre2)
+            allow = (torch.where(_near_bf16_tie(pre1) | tie_e, _bf16(pre1).abs(), torch.zeros_like(W)) +
+                     torch.where(_near_bf16_tie(pre2) | tie_e.t(), _bf16(pre2).abs(), torch.zeros_like(W))) * 2.0 ** -6
+        else:
+            pre = _f32(U * _f32(rs * kq + cs * kr))
+            W = _bf16(pre)
+            allow = torch.where(_near_bf16_tie(pre) | tie_e, W.abs() * 2.0 ** -6, torch.zeros_like(W))
+        slack = 2.0 * (allow.masked_fill(eye, 0.0) @ X.abs().amax(1)) / (float(temperature) * n) / torch.cat([vnorm, tnorm])
+    W = W.masked_fill(eye, 0.0)
+    diag = (vhat * that).sum(1) * it
+    loss = (om[:B] * (logZ[:B] - diag) + om[B:] * (logZ[B:] - diag)).sum() / n
+    return {"W": W, "X": X, "slack_rows": slack, "logZv": logZ[:B], "logZt": logZ[B:], "diag": diag, "loss": loss, "omega": om,
+            "logits": logits, "k_cols": kq, "k_rows": kr, "intra": intra, "w": w,
+            "norms": torch.cat([vnorm, tnorm]), "tau": torch.tensor(float(temperature), dtype=torch.float64),
+            "tiny": torch.cat([video.double().norm(dim=1), text.double().norm(dim=1)]) < NORM_EPS}
+
+
+def exact_weights(logits, logz_rows, logz_cols, om_rows, om_cols, k_cols, k_rows, intra, w) -> torch.Tensor:
+    """W_pq = c (exp(l_pq - logZ_p) o_p k_q + exp(l_pq - logZ_q) o_q k_p), c = w on the intra-modal blocks and 1 elsewhere, from the row
+    statistics (logz_rows, om_rows: indexed by p) and the column statistics (logz_cols, om_cols: by q).  Every exponential is relative to
+    a denominator of its own: nothing overflows at any temperature."""
+    c = torch.where(intra, torch.tensor(float(w), dtype=torch.float64), torch.tensor(1.0, dtype=torch.float64))
+    return c * (torch.exp(logits - logz_rows[:, None]) * om_rows[:, None] * k_cols + torch.exp(logits - logz_cols[None, :]) * om_cols[None, :] * k_rows)
+
+
+def grads_from_stacked_weights(model: Dict[str, torch.Tensor], W: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(grad_video, grad_text) in float64 from a `stacked_weight_model` (optionally with a modified W): the product W X, the
+    positive-pair term and the normalise-backward, all exact."""
+    X, om = model["X"], model["omega"]
+    W = model["W"] if W is None else W
+    B = X.shape[0] // 2
+    scale = 1.0 / (float(model["tau"]) * 2.0 * B)
+    G = (W @ X) * scale
+    pos = ((om[:B] + om[B:]) * scale)[:, None]
+    G[:B] -= X[B:] * pos
+    G[B:] -= X[:B] * pos
+    proj = G - X * (X * G).sum(1, keepdim=True)
+    g = torch.where(model["tiny"][:, None], G, proj) / model["norms"][:, None]
+    return g[:B], g[B:]
+
+
+def bf16_weight_model_grads(video, text, temperature=0.03, negative_weight=0.8, k=None, omega=None, saved: bool = True
+                            ) -> Dict[str, torch.Tensor]:
+    """What a correct bf16 backward returns for operands bf16 holds exactly: the two-rounding weight model of the saved backward
+    (saved=False: the one-rounding model of the recomputing kernels); see `stacked_weight_model`."""
+    m = stacked_weight_model(video, text, temperature, negative_weight, k, omega, roundings=2 if saved else 1)
+    gv, gt = grads_from_stacked_weights(m)
+    return {"loss": m["loss"], "grad_v": gv, "grad_t": gt, "logZv": m["logZv"], "logZt": m["logZt"], "diag": m["diag"]}
