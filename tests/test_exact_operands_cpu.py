@@ -167,24 +167,7 @@ def _gpu_cases():
     return sorted(set(out))
 
 
-def _tiles(B):
-    """(rows, columns) of the dropped tiles in stacked coordinates (video rows 0 .. B-1, text rows B .. 2B-1; the kernels' tiles start at each
-    modality's first row): first, last ragged, across the video / text boundary, mirrored (left of the diagonal)"""
-    last = 32 * ((B - 1) // 32)
-    second = 32 if B > 32 else 0
-    return {"first": (slice(0, 32), slice(0, 32)),
-            "last ragged": (slice(B + last, 2 * B), slice(last, B)),
-            "across the modality boundary": (slice(last, B), slice(B, B + 32)),
-            "mirrored": (slice(B + second, B + second + 32), slice(0, 32))}
-
-
-def _defective_weights(m, col_stat_shift=0, ignore_col_k=False):
-    """W of an exact model (oracle.exact_weights) with the COLUMN statistics read `col_stat_shift` columns further on, or the columns'
-    sample weights ignored -- the defects live here, not in the oracle"""
-    logz, om = torch.cat([m["logZv"], m["logZt"]]), m["omega"]
-    k_cols = torch.ones_like(m["k_cols"]) if ignore_col_k else m["k_cols"]
-    W = orc.exact_weights(m["logits"], logz, torch.roll(logz, -col_stat_shift), om, torch.roll(om, -col_stat_shift), k_cols, m["k_rows"], m["intra"], m["w"])
-    return W.masked_fill(torch.eye(W.shape[0], dtype=torch.bool), 0.0)
+_tiles, _defective_weights = xi.tiles, xi.defective_weights      # (shared with tests/test_projection_exact_cpu.py)
 
 
 _TEETH_GROUPS = {}

@@ -1,6 +1,8 @@
-"""Producer-side fusion on the emulated kernels (tiny shapes): projection + L2-norm + pack in one launch (crossclr_project_pack),
-the normalise-backward in front of the projection's backward (crossclr_project_backward_prep).  Checker: float64 autograd through
-`F.linear` and the oracle's op-for-op restatement of the reference loss (trainer/loss.py:76-114)."""
+"""Producer-side fusion on the emulated kernels (tiny shapes, random data): projection + L2-norm + pack in one launch
+(crossclr_project_pack / _wf), the split-K weight gradient (crossclr_project_dw), the module.  Checker: float64 autograd through
+`F.linear` and the oracle's op-for-op restatement of the reference loss (trainer/loss.py:76-114), at the bars bf16 products on random
+data allow.  Nothing here launches crossclr_project_backward_prep: that kernel, and every kernel above bit for bit / per element on
+exact operands, is in tests/test_projection_exact_cpu.py."""
 import pytest
 import torch
 import torch.nn.functional as F
