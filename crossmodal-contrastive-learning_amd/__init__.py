@@ -10,8 +10,8 @@ through the `crossclr_amd` alias module at the repository root:
 from . import _native
 from .loss import AUTO_BF16_MIN_GLOBAL_BATCH, CrossCLR_onlyIntraModality, all_gather_with_grad, crossclr_loss
 from .influence import CrossCLR, influential_sample_weights
-from .ranking import MaxMargin_coot, cosine_sim, max_margin_loss, retrieval_ranks, retrieval_topk
+from .ranking import MaxMargin_coot, cosine_sim, hardest_negatives, max_margin_loss, retrieval_ranks, retrieval_topk
 from .projection import ProjectedCrossCLR, projected_crossclr_loss
 
 __all__ = ["CrossCLR_onlyIntraModality", "CrossCLR", "crossclr_loss", "all_gather_with_grad", "influential_sample_weights",
-           "MaxMargin_coot", "max_margin_loss", "cosine_sim", "retrieval_ranks", "retrieval_topk", "ProjectedCrossCLR", "projected_crossclr_loss", "AUTO_BF16_MIN_GLOBAL_BATCH", "_native"]
+           "MaxMargin_coot", "max_margin_loss", "cosine_sim", "retrieval_ranks", "retrieval_topk", "hardest_negatives", "ProjectedCrossCLR", "projected_crossclr_loss", "AUTO_BF16_MIN_GLOBAL_BATCH", "_native"]

@@ -176,6 +176,13 @@ _SIGNATURES = {
     "crossclr_topk_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "crossclr_topk_select": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 6 + [_P, ctypes.c_size_t, _P]),
     "crossclr_topk_merge": (ctypes.c_int, [_P] + [ctypes.c_int] * 4 + [_P, _P, _P]),
+    # ABI version 8, additive symbols: hardest negatives / the maximum-violation form of the ranking loss
+    "crossclr_hardneg_splits": (ctypes.c_int, [ctypes.POINTER(Plan), ctypes.c_int]),
+    "crossclr_hardneg_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Plan), ctypes.c_int]),
+    "crossclr_hardneg_select": (ctypes.c_int, [ctypes.POINTER(Plan), _P, ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "crossclr_hardneg_finish": (ctypes.c_int, [ctypes.POINTER(Plan), _P, ctypes.c_int, ctypes.c_float, _P, _P, _P, _P, _P, _P]),
+    "crossclr_hardneg_backward": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _P, ctypes.c_long, ctypes.c_long, ctypes.c_int, _P, _P, _P, _P, _P,
+                                                 ctypes.c_long, ctypes.c_long, _P]),
     # ABI version 6: the whole single-device step behind two calls (the kernel-selection policy lives in the library);
     # ABI version 7: the layout crossclr_step_plan wrote is handed to both calls, the workspace is a persistent and a transient region
     "crossclr_step_plan": (ctypes.c_int, [ctypes.POINTER(Plan), ctypes.c_float, ctypes.c_float, ctypes.c_uint, ctypes.c_size_t,

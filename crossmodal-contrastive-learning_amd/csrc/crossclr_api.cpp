@@ -6,6 +6,7 @@
 #include "crossclr_kernels_generic.h"
 #include "crossclr_kernels_hvp.h"
 #include "crossclr_kernels_topk.h"
+#include "crossclr_kernels_hardneg.h"
 #include "crossclr_kernels_fast.h"
 #include "crossclr_kernels_project.h"
 #include "crossclr_kernels_saved32.h"
@@ -1573,6 +1574,102 @@ extern "C" int crossclr_topk_merge(const void* workspace, int nq, int ng, int k,
     const int lpr = ns * k > 128 ? 256 : 64, rpb = 256 / lpr;      // long candidate lists: a whole block per row
     LAUNCH(topk_merge_kernel, dim3((nq + rpb - 1) / rpb), dim3(256), stream, ws_s, ws_i, nq, nq_pad, ns, k, lpr, scores, indices);
     return launch_status("topk_merge_kernel");
+}
+
+// ------------------------------------------------------------------------------------------------
+// hardest negatives / maximum-violation ranking loss (crossclr_kernels_hardneg.h)
+static int hardneg_plan_ok(const char* what, const crossclr_plan* p) {
+    if (!p) return fail(CROSSCLR_E_ARG, "plan is NULL");
+    if (p->world != 1) return fail(CROSSCLR_E_ARG, "%s: single-device (plan->world must be 1)", what);
+    if (p->b < 1 || p->bpad < p->b || p->bpad % 128 != 0 || p->Dpad < 64 || p->Dpad % 64 != 0) return fail(CROSSCLR_E_ARG, "%s: bad plan", what);
+    return CROSSCLR_OK;
+}
+// column splits: enough thread blocks for two per CU of an MI355X (the rule of crossclr_topk_splits), at most one per column tile;
+// `requested` > 0 replaces the first rule.  Every split owns at least one tile.
+static int hardneg_splits(const crossclr_plan* p, int requested) {
+    const int ntiles = p->bpad / 128;
+    int ns = requested > 0 ? requested : (512 + ntiles - 1) / ntiles;
+    if (ns > ntiles) ns = ntiles;
+    if (ns < 1) ns = 1;
+    const int tps = (ntiles + ns - 1) / ns;
+    return (ntiles + tps - 1) / tps;
+}
+// workspace, in 4-byte words: row scores [ns][bpad] | row indices [ns][bpad] | column scores [bpad / 128][bpad] | column rows, the same |
+// positive-pair scores [bpad]
+struct HardnegWs { float* row_s; int* row_i; float* col_s; int* col_i; float* pair; };
+static size_t hardneg_ws_words(const crossclr_plan* p, int ns) { return ((size_t)2 * ns + (size_t)2 * (p->bpad / 128) + 1) * (size_t)p->bpad; }
+static HardnegWs hardneg_ws(const crossclr_plan* p, int ns, void* workspace) {
+    const size_t n = (size_t)p->bpad, nrb = (size_t)p->bpad / 128;
+    float* w = static_cast<float*>(workspace);
+    HardnegWs ws;
+    ws.row_s = w;
+    ws.row_i = reinterpret_cast<int*>(w + ns * n);
+    ws.col_s = w + 2 * ns * n;
+    ws.col_i = reinterpret_cast<int*>(w + (2 * ns + nrb) * n);
+    ws.pair = w + (2 * ns + 2 * nrb) * n;
+    return ws;
+}
+extern "C" int crossclr_hardneg_splits(const crossclr_plan* plan, int requested) {
+    if (int rc = hardneg_plan_ok("crossclr_hardneg_splits", plan)) return rc;
+    return hardneg_splits(plan, requested);
+}
+extern "C" size_t crossclr_hardneg_workspace_bytes(const crossclr_plan* plan, int splits) {
+    if (hardneg_plan_ok("crossclr_hardneg_workspace_bytes", plan)) return 0;
+    return hardneg_ws_words(plan, hardneg_splits(plan, splits)) * 4;
+}
+extern "C" int crossclr_hardneg_select(const crossclr_plan* plan, const void* xhat, int splits, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+    if (int rc = hardneg_plan_ok("crossclr_hardneg_select", plan)) return rc;
+    if (!xhat || !workspace) return fail(CROSSCLR_E_ARG, "NULL argument");
+    const int ns = hardneg_splits(plan, splits);
+    const size_t need = hardneg_ws_words(plan, ns) * 4;
+    if (workspace_bytes < need)
+        return fail(CROSSCLR_E_WORKSPACE, "crossclr_hardneg_select: workspace of %zu bytes, %zu needed (crossclr_hardneg_workspace_bytes)", workspace_bytes, need);
+    const HardnegWs ws = hardneg_ws(plan, ns, workspace);
+    const int ntiles = plan->bpad / 128, tps = (ntiles + ns - 1) / ns;
+    return with_plan_type(plan, [&](auto t) {
+        using T = typename decltype(t)::type;
+        LAUNCH((hardneg_select_kernel<T>), dim3(ntiles, ns), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad, tps, ws.row_s,
+               ws.row_i, ws.col_s, ws.col_i, ws.pair);
+        return launch_status("hardneg_select_kernel");
+    });
+}
+extern "C" int crossclr_hardneg_finish(const crossclr_plan* plan, const void* workspace, int splits, float margin, int* best_index,
+                                       float* best_score, float* hinge, float* pair_score, double* loss_sum, void* stream) {
+    if (int rc = hardneg_plan_ok("crossclr_hardneg_finish", plan)) return rc;
+    if (!workspace || !best_index || !best_score || !hinge || !pair_score || !loss_sum) return fail(CROSSCLR_E_ARG, "NULL argument");
+    if (!isfinite(margin)) return fail(CROSSCLR_E_ARG, "margin must be finite");
+    const int ns = hardneg_splits(plan, splits);
+    const HardnegWs ws = hardneg_ws(plan, ns, const_cast<void*>(workspace));
+    const int nb = plan->loss_ws_doubles - 1;
+    if (nb < 1) return fail(CROSSCLR_E_ARG, "bad plan");
+    LAUNCH(hardneg_finish_kernel, dim3(nb), dim3(256), stream, (const float*)ws.row_s, (const int*)ws.row_i, ns, (const float*)ws.col_s,
+           (const int*)ws.col_i, (const float*)ws.pair, plan->bpad, plan->b, margin, best_index, best_score, hinge, pair_score, loss_sum);
+    // loss_sum[0] = sum of the 2 B hinges, loss_sum[1] = / (B * B): the sum form's divisor (trainer/loss.py:41)
+    LAUNCH(fwd_finish_reduce_kernel, dim3(1), dim3(64), stream, loss_sum, nb, 1.0 / ((double)plan->b * (double)plan->b));
+    return launch_status("hardneg_finish_kernel");
+}
+template <typename TIN>
+static int hardneg_backward_t(const crossclr_plan* p, const void* im, const void* s, long ld_im, long ld_s, const int* best_index,
+                              const float* hinge, const double* grad_out, void* grad_im, void* grad_s, long ld_gim, long ld_gs, void* stream) {
+    LAUNCH((hardneg_backward_kernel<TIN>), dim3((p->b + 3) / 4, 2), dim3(256), stream, (const TIN*)im, (const TIN*)s, ld_im, ld_s, p->b, p->bpad,
+           p->D, best_index, hinge, grad_out, (TIN*)grad_im, (TIN*)grad_s, ld_gim, ld_gs);
+    return launch_status("hardneg_backward_kernel");
+}
+extern "C" int crossclr_hardneg_backward(const crossclr_plan* plan, const void* im, const void* s, long ld_im, long ld_s, int in_dtype,
+                                         const int* best_index, const float* hinge, const double* grad_out, void* grad_im, void* grad_s,
+                                         long ld_gim, long ld_gs, void* stream) {
+    if (int rc = hardneg_plan_ok("crossclr_hardneg_backward", plan)) return rc;
+    if (!im || !s || !best_index || !hinge || !grad_out || (!grad_im && !grad_s)) return fail(CROSSCLR_E_ARG, "NULL argument");
+    if (ld_im < plan->D || ld_s < plan->D || (grad_im && ld_gim < plan->D) || (grad_s && ld_gs < plan->D))
+        return fail(CROSSCLR_E_ARG, "row stride smaller than D");
+    switch (in_dtype) {
+        case CROSSCLR_IN_F32: return hardneg_backward_t<float>(plan, im, s, ld_im, ld_s, best_index, hinge, grad_out, grad_im, grad_s, ld_gim, ld_gs, stream);
+        case CROSSCLR_IN_F64: return hardneg_backward_t<double>(plan, im, s, ld_im, ld_s, best_index, hinge, grad_out, grad_im, grad_s, ld_gim, ld_gs, stream);
+        case CROSSCLR_IN_F16: return hardneg_backward_t<in_f16>(plan, im, s, ld_im, ld_s, best_index, hinge, grad_out, grad_im, grad_s, ld_gim, ld_gs, stream);
+        case CROSSCLR_IN_BF16: return hardneg_backward_t<in_bf16>(plan, im, s, ld_im, ld_s, best_index, hinge, grad_out, grad_im, grad_s, ld_gim, ld_gs, stream);
+    }
+    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -16,6 +16,11 @@ repository): rank of each sample's partner among all candidates of the other mod
 with margin 0 (count of candidates scoring strictly higher than the partner).  `retrieval_topk` is its other half: WHO was retrieved --
 the k best candidates of every query over two independent sets of any sizes, from the same tiled product with a selection epilogue
 (`crossclr_topk_select`, `crossclr_topk_merge`).
+
+`max_violation=True` is the hardest-negative form most COOT / VSE++ users train: one line between the reference's lines 40 and 41,
+`cost_s = cost_s.max(1)[0]; cost_im = cost_im.max(0)[0]`.  One pass over the scores with a max + argmax epilogue in both directions
+(`crossclr_hardneg_select`, `crossclr_hardneg_finish`), a sparse O(B D) gather for the gradients (`crossclr_hardneg_backward`);
+`hardest_negatives` returns the selections themselves.
 """
 from __future__ import annotations
 
@@ -109,6 +114,67 @@ class _MaxMarginFunction(torch.autograd.Function):
         return (g_im if ctx.needs_input_grad[0] else None, g_s if ctx.needs_input_grad[1] else None, None, None)
 
 
+class _HardNeg:
+    __slots__ = ("plan", "in_dtype", "index", "score", "hinge", "pair", "loss_sum")
+
+
+def _hardneg(im: torch.Tensor, s: torch.Tensor, margin: float, compute_mode: str, normalize: bool, splits: int = 0) -> _HardNeg:
+    """Select + finish: per video row the best-scoring text that is not its partner, per text column the best-scoring video, the two
+    hinges per sample and the loss.  `splits` (0 = the library's choice) cuts the launch; the result does not depend on it."""
+    lib = nat.library()
+    b, D = im.shape
+    dev = im.device
+    plan = _plan_for(b, D, 1, 0, _resolve_mode(compute_mode, b, im.dtype))
+    pp = ctypes.byref(plan)
+    stream = _stream_for(im)
+    f32 = dict(dtype=torch.float32, device=dev)
+    hn = _HardNeg()
+    hn.plan, hn.in_dtype = plan, _IN_DTYPE[im.dtype]
+    xhat = torch.empty(plan.operand_bytes, dtype=torch.uint8, device=dev)
+    inv_norm, pair_cos = torch.empty(2 * plan.bpad, **f32), torch.empty(plan.bpad, **f32)
+    lay_out = lib.crossclr_normalize if normalize else lib.crossclr_pack
+    nat.check(lay_out(pp, _ptr(im), _ptr(s), im.stride(0), s.stride(0), hn.in_dtype, _ptr(xhat), _ptr(inv_norm), _ptr(pair_cos), stream))
+    ws = torch.empty(lib.crossclr_hardneg_workspace_bytes(pp, splits), dtype=torch.uint8, device=dev)
+    nat.check(lib.crossclr_hardneg_select(pp, _ptr(xhat), splits, _ptr(ws), ws.numel(), stream))
+    hn.index = torch.empty(2 * plan.bpad, dtype=torch.int32, device=dev)
+    hn.score, hn.hinge, hn.pair = torch.empty(2 * plan.bpad, **f32), torch.empty(2 * plan.bpad, **f32), torch.empty(plan.bpad, **f32)
+    hn.loss_sum = torch.empty(plan.loss_ws_doubles, dtype=torch.float64, device=dev)
+    nat.check(lib.crossclr_hardneg_finish(pp, _ptr(ws), splits, float(margin), _ptr(hn.index), _ptr(hn.score), _ptr(hn.hinge), _ptr(hn.pair),
+                                          _ptr(hn.loss_sum), stream))
+    return hn
+
+
+class _MaxViolationFunction(torch.autograd.Function):
+    """The hardest-negative form.  Saved for backward: the two index arrays and the two hinge arrays (4 * bpad * 4 bytes) and the caller's
+    tensors -- no B x B mask, no packed operand.  Outputs: the loss and, not differentiable, the stacked selections of the pass
+    (index [2 bpad] int32 and score [2 bpad] float32: video rows, then text columns from bpad on)."""
+
+    @staticmethod
+    def forward(ctx, im, s, margin, compute_mode, splits):
+        im_c, s_c = _row_major(im.detach()), _row_major(s.detach())
+        with _device_of(im_c):
+            hn = _hardneg(im_c, s_c, margin, compute_mode, normalize=False, splits=splits)
+        ctx.plan, ctx.in_dtype = hn.plan, hn.in_dtype
+        ctx.save_for_backward(im_c, s_c, hn.index, hn.hinge)
+        ctx.mark_non_differentiable(hn.index, hn.score)
+        return hn.loss_sum[1].to(im.dtype if im.dtype != torch.float64 else torch.float64), hn.index, hn.score
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_index, _grad_score):
+        _refuse_double_backward("MaxMargin_coot")
+        im_c, s_c, index, hinge = ctx.saved_tensors
+        lib, dev = nat.library(), im_c.device
+        with _device_of(im_c):
+            go = grad_out.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
+            g_im = torch.empty_like(im_c) if ctx.needs_input_grad[0] else None
+            g_s = torch.empty_like(s_c) if ctx.needs_input_grad[1] else None
+            nat.check(lib.crossclr_hardneg_backward(ctypes.byref(ctx.plan), _ptr(im_c), _ptr(s_c), im_c.stride(0), s_c.stride(0), ctx.in_dtype,
+                                                    _ptr(index), _ptr(hinge), _ptr(go), _ptr(g_im), _ptr(g_s),
+                                                    0 if g_im is None else g_im.stride(0), 0 if g_s is None else g_s.stride(0),
+                                                    _stream_for(im_c)))
+        return g_im, g_s, None, None, None
+
+
 def _check(im: torch.Tensor, s: torch.Tensor) -> None:
     _validate(im, s)
     if not im.is_cuda and nat.backend() != "emu-host":
@@ -117,30 +183,70 @@ def _check(im: torch.Tensor, s: torch.Tensor) -> None:
         raise RuntimeError("empty batch")
 
 
-def max_margin_loss(im: torch.Tensor, s: torch.Tensor, margin: float = 0.1, *, compute_mode: str = "fp32") -> torch.Tensor:
-    """Functional form of `MaxMargin_coot.forward` (trainer/loss.py:29-41).  compute_mode="fp32" (default) = exact-fp32 products like the
-    reference's `mm`; "bf16" is opt-in: the scores are products of the caller's UN-normalised rows, so there is no a-priori error bar."""
+def _max_margin(im: torch.Tensor, s: torch.Tensor, margin: float, compute_mode: str, max_violation: bool, splits: int = 0) -> torch.Tensor:
+    """`max_margin_loss` with the number of column splits of the hardest-negative pass exposed (0 = the library's choice): the result does
+    not depend on it."""
     _check(im, s)
+    if max_violation:
+        return _MaxViolationFunction.apply(im, s, float(margin), compute_mode, int(splits))[0]
     return _MaxMarginFunction.apply(im, s, float(margin), compute_mode)
+
+
+def max_margin_loss(im: torch.Tensor, s: torch.Tensor, margin: float = 0.1, *, compute_mode: str = "fp32",
+                    max_violation: bool = False) -> torch.Tensor:
+    """Functional form of `MaxMargin_coot.forward` (trainer/loss.py:29-41).  compute_mode="fp32" (default) = exact-fp32 products like the
+    reference's `mm`; "bf16" is opt-in: the scores are products of the caller's UN-normalised rows, so there is no a-priori error bar.
+
+    max_violation=True is the hardest-negative form (VSE++; COOT's `max_violation`): `cost_s = cost_s.max(1)[0]; cost_im = cost_im.max(0)[0]`
+    between the reference's lines 40 and 41, i.e. (sum_i max_j cost_s[i, j] + sum_j max_i cost_im[i, j]) / (B * B).  The divisor stays
+    B * B so that the two forms differ by that one line: `B * loss` is VSE++'s per-sample mean.  Among bit-equal scores the lower index is
+    the hardest negative; only active hinges (> 0) carry gradient, through the caller's own tensors.  All three compute modes ("fp32",
+    "bf16", "bf16x3") are available in this form; NaN inputs are not ordered (the rows must be finite)."""
+    return _max_margin(im, s, margin, compute_mode, max_violation)
 
 
 class MaxMargin_coot(nn.Module):
     """Regular contrastive (max-margin ranking) loss between two groups of embeddings, inputs [batch, embed_dim]
     (`trainer/loss.py:17-41`; COOT, NeurIPS 2020).  Constructor arguments and attributes as the reference declares them
-    (loss.py:23-27); `use_cuda` is kept for signature compatibility -- the inputs must be on the GPU either way."""
+    (loss.py:23-27); `use_cuda` is kept for signature compatibility -- the inputs must be on the GPU either way.
+    max_violation=True: the hardest-negative form (see `max_margin_loss`)."""
 
-    def __init__(self, use_cuda: bool = True, margin: float = 0.1, *, compute_mode: str = "fp32"):
+    def __init__(self, use_cuda: bool = True, margin: float = 0.1, *, compute_mode: str = "fp32", max_violation: bool = False):
         super().__init__()
         self.margin = margin
         self.sim = cosine_sim
         self.use_cuda = use_cuda
         self.compute_mode = compute_mode
+        self.max_violation = max_violation
 
     def forward(self, im, s):
-        return max_margin_loss(im, s, self.margin, compute_mode=self.compute_mode)
+        return max_margin_loss(im, s, self.margin, compute_mode=self.compute_mode, max_violation=self.max_violation)
 
     def extra_repr(self):
-        return f"margin={self.margin}, compute_mode={self.compute_mode!r}"
+        return f"margin={self.margin}, compute_mode={self.compute_mode!r}, max_violation={self.max_violation}"
+
+
+def _hardest(im: torch.Tensor, s: torch.Tensor, normalize: bool, compute_mode: str, splits: int = 0) -> Dict[str, torch.Tensor]:
+    """`hardest_negatives` with the number of column splits exposed (0 = the library's choice): the result does not depend on it."""
+    _check(im, s)
+    v, t = _row_major(im.detach()), _row_major(s.detach())
+    with _device_of(v):
+        hn = _hardneg(v, t, 0.0, compute_mode, normalize=normalize, splits=splits)
+    b, bpad = hn.plan.b, hn.plan.bpad
+    return {"v2t_index": hn.index[:b].to(torch.int64), "t2v_index": hn.index[bpad:bpad + b].to(torch.int64),
+            "v2t_score": hn.score[:b], "t2v_score": hn.score[bpad:bpad + b], "pair_score": hn.pair[:b]}
+
+
+def hardest_negatives(video_features: torch.Tensor, text_features: torch.Tensor, *, normalize: bool = False,
+                      compute_mode: str = "fp32") -> Dict[str, torch.Tensor]:
+    """Each sample's hardest negative in both directions over S = video @ text^T (normalize=True: cosines, rows L2-normalised like the
+    loss does; default: rows as given, what `MaxMargin_coot(max_violation=True)` trains on) -- the selections of that loss's training
+    pass, from the same kernels.
+
+    Returns device tensors (no autograd, nothing synchronises the host): `v2t_index[i]` = argmax_{j != i} S[i, j] and `t2v_index[j]` =
+    argmax_{i != j} S[i, j] (int64; higher score first, among bit-equal scores the lower index; -1 when B = 1 leaves no candidate),
+    `v2t_score` / `t2v_score` (float32) the scores at those indices, `pair_score[i]` = S[i, i].  NaN inputs are not ordered."""
+    return _hardest(video_features, text_features, normalize, compute_mode)
 
 
 def retrieval_ranks(video_features: torch.Tensor, text_features: torch.Tensor, *, normalize: bool = True,

@@ -501,6 +501,42 @@ int crossclr_topk_select(const void* queries_packed, const void* gallery_packed,
                          void* workspace, size_t workspace_bytes, void* stream);
 int crossclr_topk_merge(const void* workspace, int nq, int ng, int k, int splits, float* scores, int* indices, void* stream);
 
+/* ---- hardest negatives: the maximum-violation form of the max-margin ranking loss (single device) ---------------------------
+ * VSE++ / COOT `max_violation=True`: one line between loss.py:40 and :41 -- cost_s = cost_s.max(1)[0]; cost_im = cost_im.max(0)[0] -- so
+ *   loss = ( sum_i max_j cost_s[i][j] + sum_j max_i cost_im[i][j] ) / (B * B)      (the sum form's divisor is kept)
+ * The positive pair's score is constant along a row of cost_s and a column of cost_im, so the two maxima are selections over
+ * S = im . s^T:  jr[i] = argmax_{j != i} S[i][j],  ic[j] = argmax_{i != j} S[i][j],  hr[i] = max(0, margin + S[i][jr[i]] - S[i][i]),
+ * hc[j] = max(0, margin + S[ic[j]][j] - S[j][j]).  ABI: NEW SYMBOLS ONLY, CROSSCLR_ABI_VERSION stays 8 (the policy of crossclr_topk_*).
+ *
+ * `plan` (world 1, any mode: CROSSCLR_MODE_BF16X3 included) and `xhat` are what crossclr_pack (rows as given) or crossclr_normalize
+ * (cosines) laid out.  TOTAL ORDER as in crossclr_topk_merge: higher score first, among bit-equal scores the lower index first; padding and
+ * the positive pair are masked by index.  The selections do not depend on the splits, the grid or the order blocks run in; no atomics.
+ * NaN scores are not ordered (the caller's rows must be finite).
+ * crossclr_hardneg_select  one pass over S with a max + argmax epilogue in both directions; fills `workspace`
+ *   (crossclr_hardneg_workspace_bytes; contents irrelevant before) with the partial selections and the positive pairs' scores S[i][i] --
+ *   taken from the accumulators the selections are compared with, where crossclr_score_diag refuses split-operand plans.
+ * crossclr_hardneg_finish  merges the partials in a fixed order.  Stacked outputs, entry i = video row i (jr, hr), entry bpad + j = text
+ *   column j (ic, hc): best_index[2][bpad] (int; -1 for padding entries and when B = 1 leaves no candidate), best_score[2][bpad] (float;
+ *   -inf likewise), hinge[2][bpad] (float; 0 likewise); pair_score[bpad] = S[i][i]; loss_sum (plan->loss_ws_doubles doubles):
+ *   loss_sum[0] = sum of the 2 B hinges, loss_sum[1] = that / (B * B), from double partials added in a fixed order.
+ * crossclr_hardneg_backward  the gradient of grad_out * loss w.r.t. the caller's own row-major tensors (not the packed copy), in their
+ *   dtype: only active hinges (> 0) contribute -- hr[i]: s[jr[i]] - s[i] to grad_im[i], +im[i] to grad_s[jr[i]], -im[i] to grad_s[i];
+ *   hc[j]: im[ic[j]] - im[j] to grad_s[j], +s[j] to grad_im[ic[j]], -s[j] to grad_im[j]; all scaled by grad_out[0] / (B * B) (a device
+ *   double).  An O(B D) gather in a fixed order (fp32 accumulation, fp64 for fp64 inputs); every index is checked against [0, B) before
+ *   it is used as an address.  grad_im or grad_s may be NULL (that gradient is not formed), not both.
+ * `splits`: 0 = the library's choice; > 0 = a request, cut down to what the shape allows.  Hand the SAME value to
+ *   crossclr_hardneg_workspace_bytes, _select and _finish; crossclr_hardneg_splits returns the count they derive from it.
+ * The size query returns 0 and the others CROSSCLR_E_ARG for a bad plan or argument; CROSSCLR_E_WORKSPACE for a workspace that is too
+ * small.  Nothing is allocated, nothing synchronises, everything is enqueued on `stream`.                                          */
+int crossclr_hardneg_splits(const crossclr_plan* plan, int splits);
+size_t crossclr_hardneg_workspace_bytes(const crossclr_plan* plan, int splits);
+int crossclr_hardneg_select(const crossclr_plan* plan, const void* xhat, int splits, void* workspace, size_t workspace_bytes, void* stream);
+int crossclr_hardneg_finish(const crossclr_plan* plan, const void* workspace, int splits, float margin, int* best_index, float* best_score,
+                            float* hinge, float* pair_score, double* loss_sum, void* stream);
+int crossclr_hardneg_backward(const crossclr_plan* plan, const void* im, const void* s, long ld_im, long ld_s, int in_dtype,
+                              const int* best_index, const float* hinge, const double* grad_out, void* grad_im, void* grad_s,
+                              long ld_gim, long ld_gs, void* stream);
+
 /* ---- THE WHOLE STEP BEHIND TWO CALLS (ABI 6; layout handed from call to call and split workspace: ABI 7.  Single device: plan->world == 1)
  * What the reference's one class is to its caller (trainer/loss.py:68-114 `forward`, and autograd's backward through it): a binding needs
  * nothing but crossclr_make_plan, crossclr_step_plan, crossclr_step_forward and crossclr_step_backward.  The library chooses the kernels:
