@@ -1,0 +1,160 @@
+"""Symmetric InfoNCE (CLIP) loss with a learnable logit scale.
+
+    L = 1/2 [ CE(s S, diag) + CE(s S^T, diag) ],   S = v^ . t^T
+
+The reference class carries the leftovers of this loss -- `logit_scale = nn.Parameter(torch.ones([]))` and a
+`CrossEntropyLoss(reduction='none')` child that its forward never reads; here it is a loss of its own, on the
+tiled-similarity skeleton: one pass with an online soft-max in both directions (`crossclr_infonce_stats`, `crossclr_infonce_finish`), the
+three-phase gradient product (`crossclr_infonce_backward`) and a row finish that also yields dL/ds (`crossclr_infonce_backward_finish`).
+Neither s S, the two soft-max outputs nor their gradients are materialised (eager PyTorch holds five B x B tensors), and the loss is
+available in compute_mode="bf16x3": fp32-grade logits on the bf16 matrix cores, which matters at s = 100, where a bf16 cosine error of 2^-9
+is 0.2 in the logit.
+
+The scale lives in DEVICE memory from end to end: the kernels read one fp32, nothing here calls `.item()` or `float(tensor)`, so a
+captured graph replays with whatever value the scale tensor holds then, and an optimiser can step it without a host round trip.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import torch
+from torch import nn
+
+from . import _native as nat
+from .loss import _IN_DTYPE, _device_of, _plan_for, _ptr, _refuse_double_backward, _resolve_mode, _row_major, _stream_for
+from .ranking import _check
+
+
+class _Stats:
+    __slots__ = ("plan", "in_dtype", "xhat", "inv_norm", "lse", "pair", "loss_sum")
+
+
+def _stats(video: torch.Tensor, text: torch.Tensor, scale32: torch.Tensor, mode: int, normalize: bool, splits: int = 0) -> _Stats:
+    """Lay out + statistics + finish: lse [2, 2 bpad] (log2 domain, an fp32 value and its rounding's remainder; video rows, then text
+    columns), pair [bpad] = S[i][i] and the loss.
+    `splits` (0 = the library's choice) cuts the launch."""
+    lib = nat.library()
+    b, D = video.shape
+    dev = video.device
+    plan = _plan_for(b, D, 1, 0, mode)
+    pp = ctypes.byref(plan)
+    stream = _stream_for(video)
+    f32 = dict(dtype=torch.float32, device=dev)
+    st = _Stats()
+    st.plan, st.in_dtype = plan, _IN_DTYPE[video.dtype]
+    st.xhat = torch.empty(plan.operand_bytes, dtype=torch.uint8, device=dev)
+    st.inv_norm, pair_cos = torch.empty(2 * plan.bpad, **f32), torch.empty(plan.bpad, **f32)
+    lay_out = lib.crossclr_normalize if normalize else lib.crossclr_pack
+    nat.check(lay_out(pp, _ptr(video), _ptr(text), video.stride(0), text.stride(0), st.in_dtype, _ptr(st.xhat), _ptr(st.inv_norm),
+                      _ptr(pair_cos), stream))
+    ws = torch.empty(lib.crossclr_infonce_workspace_bytes(pp, splits), dtype=torch.uint8, device=dev)
+    nat.check(lib.crossclr_infonce_stats(pp, _ptr(st.xhat), _ptr(scale32), splits, _ptr(ws), ws.numel(), stream))
+    st.lse, st.pair = torch.empty(4 * plan.bpad, **f32), torch.empty(plan.bpad, **f32)
+    st.loss_sum = torch.empty(plan.loss_ws_doubles, dtype=torch.float64, device=dev)
+    nat.check(lib.crossclr_infonce_finish(pp, _ptr(ws), splits, _ptr(scale32), _ptr(st.lse), _ptr(st.pair), _ptr(st.loss_sum), stream))
+    return st
+
+
+class _InfoNCEFunction(torch.autograd.Function):
+    """Saved for backward: the caller's tensors, the packed operand, inv_norm, lse [4 bpad], pair [bpad] and the one-element fp32 scale.  Outputs: the
+    loss and, not differentiable, lse and the positive pairs' scores."""
+
+    @staticmethod
+    def forward(ctx, video, text, scale, normalize, mode, splits):
+        v_c, t_c = _row_major(video.detach()), _row_major(text.detach())
+        with _device_of(v_c):
+            scale32 = scale.detach().reshape(1).to(torch.float32)      # (a device op: the value stays where it is)
+            st = _stats(v_c, t_c, scale32, mode, normalize, splits)
+        ctx.plan, ctx.in_dtype, ctx.normalize = st.plan, st.in_dtype, normalize
+        ctx.scale_meta = (scale.shape, scale.dtype)
+        ctx.save_for_backward(v_c, t_c, st.xhat, st.inv_norm, st.lse, st.pair, scale32)
+        ctx.mark_non_differentiable(st.lse, st.pair)
+        return st.loss_sum[1].to(torch.float64 if video.dtype == torch.float64 else torch.float32), st.lse, st.pair
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_lse, _grad_pair):
+        _refuse_double_backward("InfoNCE")
+        v_c, t_c, xhat, inv_norm, lse, pair, scale32 = ctx.saved_tensors
+        lib, plan, dev = nat.library(), ctx.plan, v_c.device
+        pp = ctypes.byref(plan)
+        need = ctx.needs_input_grad
+        with _device_of(v_c):
+            stream = _stream_for(v_c)
+            gbuf = torch.empty(plan.gbuf_bytes // 4, dtype=torch.float32, device=dev)
+            nat.check(lib.crossclr_infonce_backward(pp, _ptr(xhat), _ptr(scale32), _ptr(lse), _ptr(pair), _ptr(gbuf), stream))
+            go = grad_out.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
+            g_v = torch.empty_like(v_c) if need[0] else None
+            g_t = torch.empty_like(t_c) if need[1] else None
+            dscale = torch.empty(plan.loss_ws_doubles, dtype=torch.float64, device=dev)
+            nat.check(lib.crossclr_infonce_backward_finish(pp, _ptr(gbuf), _ptr(v_c), _ptr(t_c), v_c.stride(0), t_c.stride(0), ctx.in_dtype,
+                                                           _ptr(inv_norm), int(ctx.normalize), _ptr(scale32), _ptr(go), _ptr(g_v), _ptr(g_t),
+                                                           0 if g_v is None else g_v.stride(0), 0 if g_t is None else g_t.stride(0),
+                                                           _ptr(dscale), stream))
+            g_s = None
+            if need[2]:
+                shape, dtype = ctx.scale_meta
+                g_s = dscale[1].reshape(shape).to(dtype)
+        return g_v, g_t, g_s, None, None, None
+
+
+def _info_nce(video: torch.Tensor, text: torch.Tensor, logit_scale, normalize: bool, compute_mode: str, splits: int = 0):
+    """`info_nce_loss` with the number of column splits exposed (0 = the library's choice); returns (loss, lse [2, 2 bpad] in the log2
+    domain (value, remainder), pair_score [bpad])."""
+    _check(video, text)
+    if compute_mode == "auto":
+        raise ValueError("info_nce_loss: compute_mode='auto' is not offered (at a logit scale of 100 bf16 operands have no a-priori error "
+                         "bar); pass 'fp32', 'bf16x3' or 'bf16'")
+    mode = _resolve_mode(compute_mode, video.shape[0], video.dtype)
+    if isinstance(logit_scale, torch.Tensor):
+        if logit_scale.numel() != 1 or not logit_scale.is_floating_point():
+            raise RuntimeError(f"logit_scale must be a float or a one-element float tensor, got shape {tuple(logit_scale.shape)} "
+                               f"and dtype {logit_scale.dtype}")
+        if logit_scale.device != video.device:
+            raise RuntimeError(f"logit_scale is on {logit_scale.device}, the inputs are on {video.device}")
+        scale = logit_scale
+    else:
+        scale = torch.full((1,), float(logit_scale), dtype=torch.float32, device=video.device)
+    return _InfoNCEFunction.apply(video, text, scale, bool(normalize), mode, int(splits))
+
+
+def info_nce_loss(video_features: torch.Tensor, text_features: torch.Tensor, logit_scale=1 / 0.07, *, normalize: bool = True,
+                  compute_mode: str = "fp32") -> torch.Tensor:
+    """Symmetric InfoNCE: 1/2 [CE(s S, diag) + CE(s S^T, diag)] over S = v^ . t^T (normalize=True: cosines, rows L2-normalised like
+    `F.normalize`; normalize=False: rows as given), 0-dim, float32 (float64 for float64 inputs).
+
+    logit_scale `s`: a Python float (a constant) or a one-element float tensor on the inputs' device, which may require grad -- its
+    gradient comes back in its dtype and shape.  The value is never brought to the host.  Any finite scale is valid, 0 and negative
+    values included.  Gradients of the inputs come in their dtype; only those `requires_grad` asks for are formed.
+    compute_mode: "fp32" (default: exact-fp32 products), "bf16x3" (fp32-grade products on the bf16 matrix cores) or "bf16" (opt-in:
+    a bf16 cosine error of 2^-9 is multiplied by s in the logit); "auto" raises ValueError.  Single device; double backward raises."""
+    return _info_nce(video_features, text_features, logit_scale, normalize, compute_mode)[0]
+
+
+class InfoNCE(nn.Module):
+    """`info_nce_loss` with CLIP's parameterisation of the scale: `logit_scale` holds log(1 / temperature) -- an `nn.Parameter` when
+    `learnable`, a buffer otherwise, the `state_dict` key either way -- and the forward uses exp(logit_scale) clamped at
+    `max_logit_scale`, as torch ops on the 0-dim device tensor, so autograd chains dL/ds through them."""
+
+    def __init__(self, temperature: float = 0.07, *, learnable: bool = True, max_logit_scale: float = 100.0, normalize: bool = True,
+                 compute_mode: str = "fp32"):
+        super().__init__()
+        if not temperature > 0:
+            raise ValueError(f"temperature must be positive, got {temperature}")
+        init = torch.tensor(math.log(1.0 / temperature), dtype=torch.float32)
+        if learnable:
+            self.logit_scale = nn.Parameter(init)
+        else:
+            self.register_buffer("logit_scale", init)
+        self.learnable = learnable
+        self.max_logit_scale = max_logit_scale
+        self.normalize = normalize
+        self.compute_mode = compute_mode
+
+    def forward(self, video_features, text_features):
+        scale = self.logit_scale.exp().clamp(max=self.max_logit_scale)
+        return info_nce_loss(video_features, text_features, scale, normalize=self.normalize, compute_mode=self.compute_mode)
+
+    def extra_repr(self):
+        return (f"learnable={self.learnable}, max_logit_scale={self.max_logit_scale}, normalize={self.normalize}, "
+                f"compute_mode={self.compute_mode!r}")

@@ -537,6 +537,48 @@ int crossclr_hardneg_backward(const crossclr_plan* plan, const void* im, const v
                               const int* best_index, const float* hinge, const double* grad_out, void* grad_im, void* grad_s,
                               long ld_gim, long ld_gs, void* stream);
 
+/* ---- symmetric InfoNCE (CLIP) with a logit scale in device memory (single device) --------------------------------------------
+ *   L = 1/2 [ CE(s S, diag) + CE(s S^T, diag) ],  S = v^ . t^T:  with lr[i] = logsumexp_j s S[i][j] and lc[j] = logsumexp_i s S[i][j],
+ *   L = 1/(2B) sum_i (lr[i] + lc[i] - 2 s S[i][i]),  W[i][j] = exp(s S[i][j] - lr[i]) + exp(s S[i][j] - lc[j]) - 2 [i == j],
+ *   dL/dv^ = s/(2B) W t^,  dL/dt^ = s/(2B) W^T v^,  dL/ds = 1/(2B) sum_ij W[i][j] S[i][j].
+ * ABI: NEW SYMBOLS ONLY, CROSSCLR_ABI_VERSION stays 8 (the policy of crossclr_topk_* and crossclr_hardneg_*).
+ *
+ * `plan` (world 1, any mode: CROSSCLR_MODE_BF16X3 included) and `xhat` are what crossclr_normalize (cosines) or crossclr_pack (rows as
+ * given) laid out.  `logit_scale` points at ONE float in device memory, read by the kernels: the host never sees its value, so a captured
+ * graph replays with whatever the scalar holds then.  Any finite value is valid, 0 and negative ones included.  S, s S, the two soft-max
+ * outputs and their gradients are never materialised; every shift is the true maximum of its row or column; padding is masked by index,
+ * the positive pair is a term of both sums.  No atomics, every slot has one writer, merges run in a fixed order: the same inputs give
+ * the same bits.
+ * crossclr_infonce_stats  one pass over S with an online soft-max in both directions, in the log2 domain (x = c S, c = s log2(e)); fills
+ *   `workspace` (crossclr_infonce_workspace_bytes; contents irrelevant before) with (max, sum) partials and the positive pairs' S[i][i].
+ * crossclr_infonce_finish  merges the partials.  lse[2][2][bpad] (float): entry i = video row i over the texts, entry bpad + j = text
+ *   column j over the videos, the LOG2-DOMAIN log-sum-exp of x as an fp32 value (lse[0]) and the rounding's remainder (lse[1]):
+ *   ln 2 * (lse[0] + lse[1]) = lr / lc; 0 for padding entries -- what crossclr_infonce_backward reads; pair_score[bpad] = S[i][i]; loss_sum (plan->loss_ws_doubles doubles): loss_sum[0] = sum_i (lr[i] + lc[i] - 2 s S[i][i]),
+ *   loss_sum[1] = that / (2 B), from double partials added in a fixed order.
+ * crossclr_infonce_backward  the gradient product W . x^ of the stacked rows against the other modality, every score evaluated a second
+ *   time, the positive pair's -2 inside its tile (from `lse` and `pair_score` as crossclr_infonce_finish wrote them); fills gbuf (plan->gbuf_bytes, plan->bwd_slices slices: the layout of crossclr_backward).
+ * crossclr_infonce_backward_finish  sums the slices and writes grad_out * dL/d(video, text) w.r.t. the caller's own row-major tensors in
+ *   their dtype: g = s/(2B) M, followed by the normalize backward (g - x^ (x^ . g)) inv_norm when `normalized` (inv_norm as
+ *   crossclr_normalize wrote it; may be NULL otherwise).  grad_video or grad_text may be NULL (that gradient is not written).  dscale
+ *   (plan->loss_ws_doubles doubles): dscale[1] = grad_out * dL/ds, from the rows' <x^_p, M_p> -- no second pass over the scores.
+ *   grad_out: one device double.
+ * `splits`: 0 = the library's choice; > 0 = a request, cut down to what the shape allows.  Hand the SAME value to
+ *   crossclr_infonce_workspace_bytes, _stats and _finish; crossclr_infonce_splits returns the count they derive from it.
+ * The size query returns 0 and the others CROSSCLR_E_ARG for a bad plan or argument; CROSSCLR_E_WORKSPACE for a workspace that is too
+ * small.  Nothing is allocated, nothing synchronises, everything is enqueued on `stream`.                                          */
+int crossclr_infonce_splits(const crossclr_plan* plan, int splits);
+size_t crossclr_infonce_workspace_bytes(const crossclr_plan* plan, int splits);
+int crossclr_infonce_stats(const crossclr_plan* plan, const void* xhat, const float* logit_scale, int splits, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int crossclr_infonce_finish(const crossclr_plan* plan, const void* workspace, int splits, const float* logit_scale, float* lse,
+                            float* pair_score, double* loss_sum, void* stream);
+int crossclr_infonce_backward(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* lse,
+                              const float* pair_score, float* gbuf, void* stream);
+int crossclr_infonce_backward_finish(const crossclr_plan* plan, const float* gbuf, const void* video, const void* text, long ld_video,
+                                     long ld_text, int in_dtype, const float* inv_norm, int normalized, const float* logit_scale,
+                                     const double* grad_out, void* grad_video, void* grad_text, long ld_gvideo, long ld_gtext,
+                                     double* dscale, void* stream);
+
 /* ---- THE WHOLE STEP BEHIND TWO CALLS (ABI 6; layout handed from call to call and split workspace: ABI 7.  Single device: plan->world == 1)
  * What the reference's one class is to its caller (trainer/loss.py:68-114 `forward`, and autograd's backward through it): a binding needs
  * nothing but crossclr_make_plan, crossclr_step_plan, crossclr_step_forward and crossclr_step_backward.  The library chooses the kernels:
