@@ -40,7 +40,7 @@ from __future__ import annotations
 import ctypes
 import os
 import warnings
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -469,12 +469,20 @@ _XF_WIDTHS_DEFAULT = frozenset((512, 768, 1024, 1152, 1536, 2048, 2560, 3072, 40
 # gradient buffers compared bit for bit (a few milliseconds, once).  A difference disables the candidate for the process with a warning
 # (crossclr_backward_saved_xfp falls back to crossclr_backward_saved_xf, that one to the LDS-staged kernel).  Under HIP-graph capture
 # nothing can be verified: an unverified instantiation then takes the LDS-staged kernel.  CROSSCLR_XF_RECHECK_STEPS=N repeats the
-# self-test every N backward launches of an instantiation (default 0: never).  The tests' injected build (host emulation: no such
-# hazard exists there) skips the check.
+# self-test every N backward launches of an instantiation (default 0: never; the remote blocks' instantiations included).  The tests'
+# injected build (host emulation: no such hazard exists there) skips the check.  All of this is `_xf_gate`; its callers translate the answer.
 _xf_verified: dict = {}
 _xf_launches: dict = {}
 _XF_RECHECK = int(os.environ.get("CROSSCLR_XF_RECHECK_STEPS", "0") or 0)
 _XF_SELFTEST_ROWS = (640, 1152)
+
+
+# The self-tests' synthetic batch, aligned pairs (t = v + noise): a soft-max that is neither flat nor one-hot, so every tile carries weights
+# of mixed magnitude
+def _aligned_pair(b: int, D: int, g, dev):
+    v = torch.randn(b, D, generator=g)
+    t = (v + 0.5 * torch.randn(b, D, generator=g)).to(dev)
+    return v.to(dev), t
 
 
 def _xf_selftest(dev, D: int, weighted: bool, entry_name: str, launches: int = 3) -> bool:
@@ -489,10 +497,7 @@ def _xf_selftest(dev, D: int, weighted: bool, entry_name: str, launches: int = 3
             return None        # nothing to compare on this build / under these knobs: not a mismatch (the caller keeps the LDS-staged kernel, silently)
         pp = ctypes.byref(plan)
         g = torch.Generator().manual_seed(1000 + b)
-        # aligned pairs (t = v + noise): a soft-max that is neither flat nor one-hot, so every tile carries weights of mixed magnitude
-        v = torch.randn(b, D, generator=g)
-        t = (v + 0.5 * torch.randn(b, D, generator=g)).to(dev)
-        v = v.to(dev)
+        v, t = _aligned_pair(b, D, g, dev)
         n2 = 2 * plan.bpad
         f32 = dict(dtype=torch.float32, device=dev)
         xhat = torch.empty(plan.operand_bytes, dtype=torch.uint8, device=dev)
@@ -522,34 +527,49 @@ def _xf_selftest(dev, D: int, weighted: bool, entry_name: str, launches: int = 3
     return ok
 
 
+_XF_REMOTE = "crossclr_backward_rect_saved_xfp"      # the name the rectangular + transposed instantiations are verified under (together)
+
+
+def _xf_gate(dev, plan, weighted: bool, name: str, selftest):
+    """Is the hand-scheduled backward `name` verified on this device at this instantiation (comment above `_xf_verified`)?  True / False, or
+    None: cannot be verified right now (inside a HIP-graph capture; nothing is cached then).  The first question per instantiation -- and
+    every CROSSCLR_XF_RECHECK_STEPS-th one after it -- runs `selftest(dev, plan.D, weighted, name)`; a False verdict warns, once, and a None
+    verdict ("nothing to compare on this build") is kept as False without a warning.  The tests' injected build answers True."""
+    key = (str(dev), plan.Dpad, weighted, name, nat.library_path())
+    ok = _xf_verified.get(key)
+    if ok and _XF_RECHECK > 0:
+        n = _xf_launches[key] = _xf_launches.get(key, 0) + 1
+        if n % _XF_RECHECK == 0:
+            ok = None
+    if ok is not None:
+        return ok
+    if nat.injected_for_testing():
+        return True
+    if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+        return _xf_verified.get(key)        # nothing can be verified inside a capture: what is known stands (a recheck that fell due is skipped)
+    verdict = selftest(dev, plan.D, weighted, name)
+    if verdict is False and name == _XF_REMOTE:
+        warnings.warn(f"CrossCLR: crossclr_backward_rect_saved_xfp / _t_xfp disagree with the LDS-staged kernels on this device / build at "
+                      f"Dpad = {plan.Dpad}; remote blocks keep the LDS-staged kernels in this process")
+    elif verdict is False:
+        warnings.warn(f"CrossCLR: {name} disagrees with the LDS-staged saved backward on this device / build at Dpad = {plan.Dpad}; "
+                      "it is disabled for this process (tools/soak_xf.py reproduces the comparison)")
+    ok = _xf_verified[key] = bool(verdict)
+    return ok
+
+
 def _saved_backward_entry(ws, plan, dev) -> str:
     """Which saved backward of the local block this step launches: "crossclr_backward_saved_xfp" (pairs of tiles per barrier),
     "crossclr_backward_saved_xf", or "crossclr_backward_saved" (column tiles staged through LDS; reads the row-major operand)."""
     if ws.xf is None:
         return "crossclr_backward_saved"
-    weighted = ws.k_rows is not None
     cands = ["crossclr_backward_saved_xf"] if plan.Dpad <= 1024 else []     # (wide plans: the pair kernel or the LDS-staged one)
     if plan.stash_bytes < (1 << 32) and os.environ.get("CROSSCLR_XFP", "1") != "0":
         cands.insert(0, "crossclr_backward_saved_xfp")
     for name in cands:
-        key = (str(dev), plan.Dpad, weighted, name, nat.library_path())
-        ok = _xf_verified.get(key)
-        if ok and _XF_RECHECK > 0:
-            n = _xf_launches[key] = _xf_launches.get(key, 0) + 1
-            if n % _XF_RECHECK == 0 and not (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):
-                ok = None
+        ok = _xf_gate(dev, plan, ws.k_rows is not None, name, _xf_selftest)
         if ok is None:
-            if nat.injected_for_testing():
-                ok = True
-            elif dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
-                return "crossclr_backward_saved"          # nothing can be verified inside a capture
-            else:
-                ok = _xf_selftest(dev, plan.D, weighted, name)
-                if ok is False:
-                    import warnings
-                    warnings.warn(f"CrossCLR: {name} disagrees with the LDS-staged saved backward on this device / build at Dpad = {plan.Dpad}; "
-                                  "it is disabled for this process (tools/soak_xf.py reproduces the comparison)")
-            _xf_verified[key] = ok = bool(ok)
+            break           # unverifiable: the LDS-staged kernel
         if ok:
             return name
     return "crossclr_backward_saved"
@@ -591,43 +611,35 @@ def _sw(k_rows, k_cols, lw) -> "ctypes.POINTER(nat.SampleWeights) | None":
     return ctypes.pointer(s)
 
 
+def _abi(ws):      # (library, plan, the plan as the C-ABI takes it): what every stage of a step calls through
+    return nat.library(), ws.plan, ctypes.byref(ws.plan)
+
+
 _last_step_backward_kernel = None     # crossclr_step_layout.backward_kernel of the most recent single-device forward (tests, bench.py)
 _last_step_saved = None               # ... and whether that step saved its exponentials
+
+
+# crossclr_step_layout.backward_kernel -> (entry point, the flag that takes it out of the library's choice)
+_STEP_XF_KERNELS = {3: ("crossclr_backward_saved_xfp", nat.STEP_NO_XFP), 2: ("crossclr_backward_saved_xf", nat.STEP_NO_XF)}
 
 
 def _step_flags(plan, flags: int, temperature: float, negative_w: float, weighted: bool, dev) -> "tuple[int, nat.StepLayout]":
     """The single-device step's flags after this module's one reservation about the library's choice: a hand-scheduled fragment-major
     backward (crossclr_backward_saved_xfp / _xf) is only taken once it has reproduced the LDS-staged kernel bit for bit on this device
-    (`_xf_selftest`, once per instantiation); a rejected -- or, inside a HIP-graph capture, unverifiable -- one is taken out with
-    CROSSCLR_STEP_NO_XFP / _NO_XF and the library plans again.  Everything else (two-pass regime, save or recompute, layouts) is
-    crossclr_step_plan's decision."""
+    (`_xf_gate` with `_xf_selftest`, once per instantiation); a rejected one is taken out with its CROSSCLR_STEP_NO_XFP / _NO_XF, an
+    unverifiable one (inside a HIP-graph capture) with both, and the library plans again.  Everything else (two-pass regime, save or
+    recompute, layouts) is crossclr_step_plan's decision."""
     lib = nat.library()
     lay = nat.StepLayout()
-    names = {3: ("crossclr_backward_saved_xfp", nat.STEP_NO_XFP), 2: ("crossclr_backward_saved_xf", nat.STEP_NO_XF)}
     while True:
         nat.check(lib.crossclr_step_plan(ctypes.byref(plan), temperature, negative_w, flags, 0, ctypes.byref(lay)))
-        cand = names.get(lay.backward_kernel)
-        if cand is None or nat.injected_for_testing():
+        cand = _STEP_XF_KERNELS.get(lay.backward_kernel)
+        if cand is None:
             return flags, lay
-        name, off_flag = cand
-        key = (str(dev), plan.Dpad, weighted, name, nat.library_path())
-        ok = _xf_verified.get(key)
-        if ok and _XF_RECHECK > 0:
-            n = _xf_launches[key] = _xf_launches.get(key, 0) + 1
-            if n % _XF_RECHECK == 0 and not (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):
-                ok = None
-        if ok is None:
-            if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
-                flags |= nat.STEP_NO_XFP | nat.STEP_NO_XF       # nothing can be verified inside a capture: the LDS-staged kernel
-                continue
-            verdict = _xf_selftest(dev, plan.D, weighted, name)
-            if verdict is False:
-                warnings.warn(f"CrossCLR: {name} disagrees with the LDS-staged saved backward on this device / build at Dpad = {plan.Dpad}; "
-                              "it is disabled for this process (tools/soak_xf.py reproduces the comparison)")
-            ok = _xf_verified[key] = bool(verdict)
+        ok = _xf_gate(dev, plan, weighted, cand[0], _xf_selftest)
         if ok:
             return flags, lay
-        flags |= off_flag
+        flags |= cand[1] if ok is False else nat.STEP_NO_XFP | nat.STEP_NO_XF
 
 
 def _forward_step(video, text, temperature, negative_w, plan, mode, negative_scale, loss_weight, save_for_backward, prenormalized):
@@ -636,16 +648,7 @@ def _forward_step(video, text, temperature, negative_w, plan, mode, negative_sca
     it for the tools and tests that look at intermediate results."""
     lib = nat.library()
     dev = video.device
-    b = video.shape[0]
-    ws = _Workspace()
-    ws.plan, ws.world, ws.rank, ws.sharded = plan, 1, 0, False
-    ws.temperature, ws.negative_w = float(temperature), float(negative_w)
-    ws.in_dtype = _IN_DTYPE[video.dtype]
-    ws.group = ws.partner_peers = ws.exchange = ws.k_work = ws.stats_work = None
-    ws.saved_blocks = ws.recompute_ranges = ws.xf_all = None
-    ws.k_rows = _pack_pair(negative_scale, b, plan.bpad, dev, "negative_scale")
-    ws.lw = _pack_pair(loss_weight, b, plan.bpad, dev, "loss_weight")
-    ws.k_cols = ws.k_rows
+    ws = _new_workspace(plan, video, temperature, negative_w, negative_scale, loss_weight)
     ws.prenormalized = bool(prenormalized)
     flags = (nat.STEP_PRENORMALIZED if prenormalized else 0) | (0 if save_for_backward else nat.STEP_FORWARD_ONLY)
     # With a backward to follow the forward call also enqueues the gradient product (it does not depend on grad_out): the GPU keeps working
@@ -693,18 +696,22 @@ def _forward_step(video, text, temperature, negative_w, plan, mode, negative_sca
     return ws.loss_sum[1], ws      # = sum / (2 B), written by the finish kernel
 
 
+def _grad_buffers(video, text, grad_out):     # (grad_out as one float64 on the inputs' device, the two gradient outputs) for the backward's finish
+    dev = video.device
+    if grad_out.dtype == torch.float64 and grad_out.device == dev and grad_out.numel() == 1:
+        go = grad_out.detach().reshape(1)
+    else:
+        go = grad_out.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
+    return go, torch.empty(video.shape, dtype=video.dtype, device=dev), torch.empty(text.shape, dtype=text.dtype, device=dev)
+
+
 def _backward_step(ws, video, text, grad_out):
     lib = nat.library()
     plan = ws.plan
     dev = video.device
     lay, persistent, transient = ws.step
     scratch = torch.empty(lay.backward_scratch_bytes, dtype=torch.uint8, device=dev) if lay.backward_scratch_bytes else None
-    if grad_out.dtype == torch.float64 and grad_out.device == dev and grad_out.numel() == 1:
-        go = grad_out.detach().reshape(1)
-    else:
-        go = grad_out.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
-    gv = torch.empty(video.shape, dtype=video.dtype, device=dev)
-    gt = torch.empty(text.shape, dtype=text.dtype, device=dev)
+    go, gv, gt = _grad_buffers(video, text, grad_out)
     with _Range("crossclr.step_backward"):
         nat.check(lib.crossclr_step_backward(ctypes.byref(plan), ctypes.byref(lay), _ptr(video), _ptr(text), video.stride(0), text.stride(0),
                                              ws.in_dtype, _sw(ws.k_rows, ws.k_rows, ws.lw), _ptr(persistent), _ptr(transient),
@@ -713,6 +720,151 @@ def _backward_step(ws, video, text, grad_out):
     #  -- retain_graph=True -- finds transient == None and the library recomputes the product from the persistent region)
     ws.release_transient()
     return gv, gt
+
+
+# What one forward decides from the plan, the temperature regime, `save_for_backward`, the ranks' agreement about their stashes and the
+# environment -- facts every rank has in common, read ONCE per forward: every rank must take the same decisions (what travels, which
+# collectives are entered), so no stage decides any of them again.  What depends on this rank's own allocations (did it get its stash?) is
+# not in here: that is settled where the allocation happens.
+class _Scheme(NamedTuple):
+    save: bool                          # a backward will follow
+    use_xf: bool                        # the packing launch also leaves the fragment-major copy (crossclr_backward_saved_xf / _xfp)
+    use_pairs: bool = False             # pair evaluation of the remote blocks (bf16 register-resident path, >= 3 ranks)
+    npairs: int = 0
+    peers: tuple = ()                   # the pair partners this rank evaluates, rank + 1 .. rank + npairs: the order the forward needs them in
+    opp: Optional[int] = None           # the antipodal rank (at 2 ranks: the other rank); None with an odd number of ranks
+    exchange: str = "allgather"         # | "p2p" | "p2p_each"
+    first_peers: Optional[list] = None  # point-to-point exchange: the slices that travel first (peers + antipode); None: one all-gather
+    partner_possible: bool = False      # partner gradients -- which need this rank's stash
+    save_pair_blocks: bool = False      # the remote blocks this rank evaluates save their exponentials, if the local block saved its own
+    save_all_remote: bool = False       # exact-fp32 / wide plans: so does the one block against all other ranks, on the same condition
+    exchange_shifts: bool = False       # two-pass regime: row maxima exchanged between the passes (the remote block saves U and Ut)
+
+
+def _scheme_for(plan, sharded: bool, small_tau: bool, save: bool, stash_everywhere: bool) -> _Scheme:
+    lib, pp = nat.library(), ctypes.byref(plan)
+    world, rank = plan.world, plan.rank
+    env = os.environ.get
+    # With a saved backward to follow (plan.xf_bytes > 0: bf16 register-resident path, D <= 512) the packing launch also leaves the
+    # unit rows in the fragment-major layout that backward loads straight into MFMA fragments (crossclr_backward_saved_xf).
+    use_xf = save and plan.xf_bytes > 0 and plan.stash_bytes > 0 and not small_tau and _use_xf(plan)
+    if not sharded:
+        return _Scheme(save, use_xf)
+    # CROSSCLR_DISABLE_PAIR_FORWARD=1: every rank evaluates all blocks.  CROSSCLR_DISABLE_REMOTE_SAVE=1: remote blocks recompute.
+    use_pairs = world >= 3 and plan.fast_path == 1 and not small_tau and env("CROSSCLR_DISABLE_PAIR_FORWARD") != "1"
+    remote_save = save and env("CROSSCLR_DISABLE_REMOTE_SAVE") != "1"
+    npairs = (world - 1) // 2 if use_pairs else 0
+    peers = tuple((rank + 1 + k) % world for k in range(npairs))
+    opp = (rank + world // 2) % world if world % 2 == 0 else None
+    exchange = _exchange_mode(world, use_pairs)
+    rect1 = plan.fast_path == 1 and not small_tau and lib.crossclr_rect_stash_bytes(pp, 1) > 0      # (0 beyond D = 1024: the register-resident kernels end there)
+    # Partner gradients (default with the pair scheme and a backward to follow): the rank that evaluated a pair block also forms
+    # that block's contribution to its partner's gradient from the saved exponentials and ships it, instead of the partner
+    # recomputing the block.  Decided from rank-invariant facts only (every rank must agree on what travels).
+    partner_possible = (remote_save and use_pairs and plan.stash_bytes > 0 and stash_everywhere and rect1 and
+                        env("CROSSCLR_PARTNER_GRADS", "1") != "0")
+    first_peers = None
+    if use_pairs and exchange in ("p2p", "p2p_each"):
+        first_peers = list(peers) + ([opp] if opp is not None else [])
+    save_all = remote_save and world >= 2 and not small_tau and stash_everywhere and (plan.mode == nat.MODE_FP32 or plan.Dpad > 1024)
+    shifts = (remote_save and small_tau and int(lib.crossclr_rect_stash_bytes_s(pp, world - 1)) > 0 and
+              int(lib.crossclr_stash_bytes_s(pp)) > 0)
+    return _Scheme(save, use_xf, use_pairs, npairs, peers, opp, exchange, first_peers, partner_possible,
+                   save_pair_blocks=remote_save and rect1 and (use_pairs or world == 2), save_all_remote=save_all, exchange_shifts=shifts)
+
+
+# What either step path records before its first launch (single device, no group: the sharded path overwrites `sharded` / `group`).
+# The buffers themselves are left unset: the step path carves them on first use (`_Workspace.__getattr__`).
+def _new_workspace(plan, video, temperature, negative_w, negative_scale, loss_weight) -> _Workspace:
+    b, dev = video.shape[0], video.device
+    ws = _Workspace()
+    ws.plan, ws.world, ws.rank, ws.sharded = plan, plan.world, plan.rank, False
+    ws.temperature, ws.negative_w = float(temperature), float(negative_w)
+    ws.in_dtype = _IN_DTYPE[video.dtype]
+    ws.group = ws.partner_peers = ws.exchange = ws.k_work = ws.stats_work = None
+    ws.saved_blocks = ws.recompute_ranges = ws.xf_all = ws.step = ws.lazy = None
+    ws.k_rows = _pack_pair(negative_scale, b, plan.bpad, dev, "negative_scale")
+    ws.lw = _pack_pair(loss_weight, b, plan.bpad, dev, "loss_weight")
+    ws.k_cols = ws.k_rows
+    return ws
+
+
+def _carve_slab(ws, dev) -> torch.Tensor:       # returns `part`, the forward's partial sums (one group of plan.fwd_slots per launch)
+    # one allocation for everything the step keeps (a dozen torch.empty calls were a third of the host time at small batches):
+    # [xhat | loss_sum (doubles) | inv_norm | diag | logz | rz | wrz | part], every piece 256-byte aligned
+    plan = ws.plan
+    n2 = 2 * plan.bpad
+    sizes = [plan.operand_bytes, 0, 4 * n2, 4 * plan.bpad, 4 * n2, 4 * n2, 4 * n2, 4 * plan.fwd_ws_floats]
+    offs, tot = [], 0
+    for sz in sizes:
+        offs.append(tot)
+        tot += (sz + 255) // 256 * 256
+    slab = torch.empty(tot, dtype=torch.uint8, device=dev)
+    ws.xhat = slab[offs[0]:offs[0] + sizes[0]]
+    # (the loss the caller gets back is a 0-dim view of this buffer: its own small allocation, so it never pins the slab)
+    ws.loss_sum = torch.empty(max(2, plan.loss_ws_doubles), dtype=torch.float64, device=dev)
+    ws.inv_norm = _carve(slab, offs[2], sizes[2], torch.float32)
+    ws.diag = _carve(slab, offs[3], sizes[3], torch.float32)
+    ws.logz = _carve(slab, offs[4], sizes[4], torch.float32)
+    ws.rz = _carve(slab, offs[5], sizes[5], torch.float32)
+    ws.wrz = _carve(slab, offs[6], sizes[6], torch.float32)
+    return _carve(slab, offs[7], sizes[7], torch.float32)
+
+
+# normalize / pack / project: unit rows in the kernels' layout (ws.xhat, for a fragment-major saved backward also ws.xf), 1 / ||x||, cosines
+def _pack_operands(ws, scheme, video, text, project, stream) -> None:
+    lib, plan, pp = _abi(ws)
+    # (fused projection in a sharded run: the remote blocks read row-major operands, no fragment-major copy)
+    use_xf = scheme.use_xf and (project is None or plan.world == 1)
+    ws.xf = torch.empty(plan.xf_bytes, dtype=torch.uint8, device=video.device) if use_xf else None
+    if project is not None:
+        if plan.fast_path != 1 or plan.Dpad > 1024 or plan.mode != nat.MODE_BF16:
+            raise RuntimeError("the fused projection needs the bf16 register-resident path (embed_dim <= 1024)")
+        wv, wt, ldws, bias_v, bias_t, _ = project
+        with _Range("crossclr.project_pack"):
+            nat.check(lib.crossclr_project_pack_wf(pp, _ptr(video), _ptr(text), video.stride(0), text.stride(0), video.shape[1], text.shape[1],
+                                                ws.in_dtype, _ptr(wv), _ptr(wt), ldws[0], ldws[1], _ptr(bias_v), _ptr(bias_t), _ptr(ws.xhat),
+                                                _ptr(ws.inv_norm), _ptr(ws.diag), stream))
+            # the saved backward's fragment-major copy, re-laid from the packed rows (16 MiB at b = 8192, D = 512: a few microseconds
+            # against the ~10 % the fragment-major backward is faster by)
+            if ws.xf is not None:
+                nat.check(lib.crossclr_pack_xf_from_packed(pp, ws.xhat.data_ptr(), 1, ws.xf.data_ptr(), stream))
+        return
+    with _Range("crossclr.normalize"):
+        if ws.xf is not None:
+            entry = lib.crossclr_pack_xf if ws.prenormalized else lib.crossclr_normalize_xf
+            nat.check(entry(pp, _ptr(video), _ptr(text), video.stride(0), text.stride(0), ws.in_dtype,
+                            _ptr(ws.xhat), _ptr(ws.xf), _ptr(ws.inv_norm), _ptr(ws.diag), stream))
+        else:
+            entry = lib.crossclr_pack if ws.prenormalized else lib.crossclr_normalize    # unit rows are only laid out, not re-normalised
+            nat.check(entry(pp, _ptr(video), _ptr(text), video.stride(0), text.stride(0), ws.in_dtype,
+                            _ptr(ws.xhat), _ptr(ws.inv_norm), _ptr(ws.diag), stream))
+
+
+def _start_exchange(ws, scheme) -> None:        # the ranks' packed operands (and negative scales) set off towards each other; nothing waits here
+    global _last_exchange_mode
+    if not ws.sharded:
+        ws.xcols = ws.xhat
+        return
+    import torch.distributed as dist
+    dev = ws.xhat.device
+    # all-gather of the packed operands runs on the collective's own stream (RCCL over xGMI)
+    # while the local column block is processed on the compute stream
+    ws.xcols = torch.empty(ws.world * ws.plan.operand_bytes, dtype=torch.uint8, device=dev)
+    ws.exchange = _OperandExchange(ws.xcols, ws.xhat, ws.group, ws.world, ws.rank, scheme.first_peers, each=(scheme.exchange == "p2p_each"),
+                                   defer_late=scheme.partner_possible)
+    _last_exchange_mode = ws.exchange.mode
+    if ws.k_rows is not None:   # (asynchronous: the local block does not need the other ranks' negative scales)
+        ws.k_cols = torch.empty(ws.world * ws.k_rows.numel(), dtype=torch.float32, device=dev)
+        ws.k_work = dist.all_gather_into_tensor(ws.k_cols, ws.k_rows, group=ws.group, async_op=True)
+
+
+# waits for the asynchronous gather of the other ranks' negative scales (ws.k_cols) -- every launch over the gathered operand
+# reads them, in the forward and in the backward (`ws.exchange.wait()` covers the operand exchange only)
+def _k_cols_ready(ws) -> None:
+    if ws.k_work is not None:
+        _traced_wait("negative scales", [ws.k_work])
+        ws.k_work = None
 
 
 def _forward_impl(video: torch.Tensor, text: torch.Tensor, temperature: float, negative_w: float,
@@ -750,117 +902,43 @@ def _forward_impl(video: torch.Tensor, text: torch.Tensor, temperature: float, n
             nblocks = (world - 1) // 2 + (1 if world % 2 == 0 else 0)
             need = int(plan.stash_bytes + nblocks * lib.crossclr_rect_stash_bytes(ctypes.byref(plan), 1))
         stash_everywhere = _check_equal_rows_per_rank(b, D, group, dev, need)
+    scheme = _scheme_for(plan, sharded, small_tau, save_for_backward, stash_everywhere)
     stream = _stream_for(video)
-    f32 = dict(dtype=torch.float32, device=dev)
-
-    ws = _Workspace()
-    ws.step = None
-    ws.plan, ws.world, ws.rank, ws.sharded = plan, world, rank, sharded
-    ws.temperature, ws.negative_w = float(temperature), float(negative_w)
-    ws.in_dtype = _IN_DTYPE[video.dtype]
-    # one allocation for everything the step keeps (a dozen torch.empty calls were a third of the host time at small batches):
-    # [xhat | loss_sum (doubles) | inv_norm | diag | logz | rz | wrz | part], every piece 256-byte aligned
-    n2 = 2 * plan.bpad
-    sizes = [plan.operand_bytes, 0, 4 * n2, 4 * plan.bpad, 4 * n2, 4 * n2, 4 * n2, 4 * plan.fwd_ws_floats]
-    offs, tot = [], 0
-    for sz in sizes:
-        offs.append(tot)
-        tot += (sz + 255) // 256 * 256
-    slab = torch.empty(tot, dtype=torch.uint8, device=dev)
-    ws.xhat = slab[offs[0]:offs[0] + sizes[0]]
-    # (the loss the caller gets back is a 0-dim view of this buffer: its own small allocation, so it never pins the slab)
-    ws.loss_sum = torch.empty(max(2, plan.loss_ws_doubles), dtype=torch.float64, device=dev)
-    ws.inv_norm = _carve(slab, offs[2], sizes[2], torch.float32)
-    ws.diag = _carve(slab, offs[3], sizes[3], torch.float32)
-    ws.logz = _carve(slab, offs[4], sizes[4], torch.float32)
-    ws.rz = _carve(slab, offs[5], sizes[5], torch.float32)
-    ws.wrz = _carve(slab, offs[6], sizes[6], torch.float32)
-    part = _carve(slab, offs[7], sizes[7], torch.float32)
-    nlaunch = 2 if sharded else 1
-    pp = ctypes.byref(plan)
-    ws.group, ws.partner_peers = group, None
-    partner_possible = False
-    ws.k_rows = _pack_pair(negative_scale, b, plan.bpad, dev, "negative_scale")
-    ws.lw = _pack_pair(loss_weight, b, plan.bpad, dev, "loss_weight")
-    ws.k_cols = ws.k_rows
-
+    ws = _new_workspace(plan, video, temperature, negative_w, negative_scale, loss_weight)
+    ws.sharded, ws.group = sharded, group
     ws.prenormalized = bool(prenormalized) or project is not None
-    ws.xf = ws.xf_all = None
-    if project is not None:
-        if plan.fast_path != 1 or plan.Dpad > 1024 or mode != nat.MODE_BF16:
-            raise RuntimeError("the fused projection needs the bf16 register-resident path (embed_dim <= 1024)")
-        wv, wt, ldws, bias_v, bias_t, _ = project
-        with _Range("crossclr.project_pack"):
-            nat.check(lib.crossclr_project_pack_wf(pp, _ptr(video), _ptr(text), video.stride(0), text.stride(0), video.shape[1], text.shape[1],
-                                                ws.in_dtype, _ptr(wv), _ptr(wt), ldws[0], ldws[1], _ptr(bias_v), _ptr(bias_t), _ptr(ws.xhat),
-                                                _ptr(ws.inv_norm), _ptr(ws.diag), stream))
-            # the saved backward's fragment-major copy, re-laid from the packed rows (16 MiB at b = 8192, D = 512: a few microseconds
-            # against the ~10 % the fragment-major backward is faster by)
-            if save_for_backward and plan.xf_bytes > 0 and plan.stash_bytes > 0 and not small_tau and _use_xf(plan) and world == 1:
-                ws.xf = torch.empty(plan.xf_bytes, dtype=torch.uint8, device=dev)
-                nat.check(lib.crossclr_pack_xf_from_packed(pp, ws.xhat.data_ptr(), 1, ws.xf.data_ptr(), stream))
-    else:
-        # With a saved backward to follow (plan.xf_bytes > 0: bf16 register-resident path, D <= 512) the same launch also leaves the
-        # unit rows in the fragment-major layout that backward loads straight into MFMA fragments (crossclr_backward_saved_xf).
-        use_xf = save_for_backward and plan.xf_bytes > 0 and plan.stash_bytes > 0 and not small_tau and _use_xf(plan)
-        ws.xf = torch.empty(plan.xf_bytes, dtype=torch.uint8, device=dev) if use_xf else None
-        with _Range("crossclr.normalize"):
-            if ws.xf is not None:
-                entry = lib.crossclr_pack_xf if prenormalized else lib.crossclr_normalize_xf
-                nat.check(entry(pp, _ptr(video), _ptr(text), video.stride(0), text.stride(0), ws.in_dtype,
-                                _ptr(ws.xhat), _ptr(ws.xf), _ptr(ws.inv_norm), _ptr(ws.diag), stream))
-            else:
-                entry = lib.crossclr_pack if prenormalized else lib.crossclr_normalize    # unit rows are only laid out, not re-normalised
-                nat.check(entry(pp, _ptr(video), _ptr(text), video.stride(0), text.stride(0), ws.in_dtype,
-                                _ptr(ws.xhat), _ptr(ws.inv_norm), _ptr(ws.diag), stream))
-    gather = None
-    if sharded:
-        # all-gather of the packed operands runs on the collective's own stream (RCCL over xGMI)
-        # while the local column block is processed on the compute stream
-        ws.xcols = torch.empty(world * plan.operand_bytes, dtype=torch.uint8, device=dev)
-        first_peers = None
-        # Partner gradients (default with the pair scheme and a backward to follow): the rank that evaluated a pair block also forms
-        # that block's contribution to its partner's gradient from the saved exponentials and ships it, instead of the partner
-        # recomputing the block.  Decided from rank-invariant facts only (every rank must agree on what travels).
-        partner_possible = (save_for_backward and world >= 3 and plan.fast_path == 1 and plan.stash_bytes > 0 and not small_tau and stash_everywhere and
-                            os.environ.get("CROSSCLR_DISABLE_PAIR_FORWARD") != "1" and os.environ.get("CROSSCLR_DISABLE_REMOTE_SAVE") != "1" and
-                            os.environ.get("CROSSCLR_PARTNER_GRADS", "1") != "0" and lib.crossclr_rect_stash_bytes(pp, 1) > 0)
-        pairs_apply = world >= 3 and plan.fast_path == 1 and not small_tau and os.environ.get("CROSSCLR_DISABLE_PAIR_FORWARD") != "1"
-        xmode = _exchange_mode(world, pairs_apply)
-        if xmode in ("p2p", "p2p_each") and pairs_apply:
-            first_peers = [(rank + 1 + k) % world for k in range((world - 1) // 2)]     # in the order the forward needs them
-            if world % 2 == 0:
-                first_peers.append((rank + world // 2) % world)
-        gather = ws.exchange = _OperandExchange(ws.xcols, ws.xhat, group, world, rank, first_peers, each=(xmode == "p2p_each"),
-                                                defer_late=partner_possible)
-        global _last_exchange_mode
-        _last_exchange_mode = gather.mode
-        ws.k_work = None
-        if ws.k_rows is not None:   # (asynchronous: the local block does not need the other ranks' negative scales)
-            ws.k_cols = torch.empty(world * ws.k_rows.numel(), **f32)
-            ws.k_work = dist.all_gather_into_tensor(ws.k_cols, ws.k_rows, group=group, async_op=True)
-    else:
-        ws.xcols = ws.xhat
-        ws.exchange = None
-        ws.k_work = None
-
-    def k_cols_ready():
-        if ws.k_work is not None:
-            _traced_wait("negative scales", [ws.k_work])
-            ws.k_work = None
+    part = _carve_slab(ws, dev)
+    _pack_operands(ws, scheme, video, text, project, stream)
+    _start_exchange(ws, scheme)
     # Small temperatures (max |logit| = max(1,|w|)/tau > 128): no single soft-max shift fits fp32.  Like the reference's
     # float64 soft-max (loss.py:60) the rows then get their own shift -- the row maximum, found by a first pass -- and the
     # generic tiled kernels do the rest (no symmetric evaluation, no pair scheme, no save-for-backward in this regime).
     ws.shift = ws.shift_cols = None
-    if lib.crossclr_needs_row_shift(ws.temperature, ws.negative_w):
-        return _forward_row_shift(lib, ws, part, gather, group, stream, b, world, rank, dev, save_for_backward, k_cols_ready)
-    # Local (symmetric) block.  When a backward will follow and the plan offers it, the forward also saves its bf16
-    # exponentials (plan.stash_bytes, 0.27 GB at b = 8192) so that the backward does not recompute the similarity
-    # product -- the analogue of the reference's autograd-saved [B,2B] float64 tensors, 50x smaller.
-    ws.stash = _alloc_stash(plan.stash_bytes, dev) if save_for_backward else None
+    if small_tau:
+        nlaunch = _forward_row_shift(ws, scheme, part, stream)
+    else:
+        _forward_local(ws, scheme, part, stream)
+        # With a backward to follow, the remote blocks this rank evaluates itself (pair partners, antipodal rank; at 2 ranks: the
+        # other rank) save their exponentials as well: the backward then recomputes only the blocks the OTHER ranks evaluated.
+        save_remote = scheme.save_pair_blocks and ws.stash is not None
+        if sharded and (save_remote or scheme.use_pairs):
+            nlaunch = _forward_pair_blocks(ws, scheme, part, stream, save_remote)
+        elif sharded:
+            nlaunch = _forward_all_remote(ws, scheme, part, stream)
+        else:
+            nlaunch = 1
+    return _forward_finish(ws, scheme, part, nlaunch, stream), ws
+
+
+# Local (symmetric) block.  When a backward will follow and the plan offers it, the forward also saves its bf16
+# exponentials (plan.stash_bytes, 0.27 GB at b = 8192) so that the backward does not recompute the similarity
+# product -- the analogue of the reference's autograd-saved [B,2B] float64 tensors, 50x smaller.
+def _forward_local(ws, scheme, part, stream) -> None:
+    lib, plan, pp = _abi(ws)
+    ws.stash = _alloc_stash(plan.stash_bytes, part.device) if scheme.save else None
     if ws.stash is None:
         ws.xf = None      # (no saved backward after all: the recomputing one reads the row-major operand)
-    if partner_possible and ws.stash is None:
+    if scheme.partner_possible and ws.stash is None:
         raise RuntimeError("CrossCLR (sharded): could not allocate the saved-exponentials buffer on this rank; the ranks agreed on the "
                            "partner-gradient scheme, which needs it -- set CROSSCLR_PARTNER_GRADS=0 (or CROSSCLR_DISABLE_SAVE=1) on every rank")
     with _Range("crossclr.forward"):
@@ -868,213 +946,195 @@ def _forward_impl(video: torch.Tensor, text: torch.Tensor, temperature: float, n
             nat.check(lib.crossclr_forward_save(pp, _ptr(ws.xhat), ws.temperature, ws.negative_w,
                                                 _sw(ws.k_rows, ws.k_rows, None), _ptr(part), 0, _ptr(ws.stash), stream))
         else:
-            nat.check(lib.crossclr_forward_w(pp, _ptr(ws.xhat), _ptr(ws.xhat), 1, rank, -1, ws.temperature, ws.negative_w,
+            nat.check(lib.crossclr_forward_w(pp, _ptr(ws.xhat), _ptr(ws.xhat), 1, ws.rank, -1, ws.temperature, ws.negative_w,
                                              _sw(ws.k_rows, ws.k_rows, None), _ptr(part), 0, stream))
-    # Pair evaluation (bf16 register-resident path, >= 3 ranks): the (r, s) block of the symmetric matrix of exponentials
-    # is evaluated by ONE of the two ranks, which ships its column sums to the other -- 3 instead of 7 remote blocks at
-    # 8 ranks (+ the antipodal one, evaluated by both).  CROSSCLR_DISABLE_PAIR_FORWARD=1: every rank evaluates all blocks.
-    use_pairs = (sharded and plan.fast_path == 1 and world >= 3 and
-                 os.environ.get("CROSSCLR_DISABLE_PAIR_FORWARD") != "1")
-    # With a backward to follow, the remote blocks this rank evaluates itself (pair partners, antipodal rank; at 2 ranks: the
-    # other rank) save their exponentials as well: the backward then recomputes only the blocks the OTHER ranks evaluated.
-    ws.saved_blocks, ws.recompute_ranges = None, None
-    save_remote = (sharded and world >= 2 and ws.stash is not None and plan.fast_path == 1 and (use_pairs or world == 2) and
-                   lib.crossclr_rect_stash_bytes(pp, 1) > 0 and   # (0 beyond D = 1024: the register-resident kernels end there)
-                   os.environ.get("CROSSCLR_DISABLE_REMOTE_SAVE") != "1")
-    npairs = (world - 1) // 2 if use_pairs else 0
-    if sharded and (save_remote or use_pairs):
-        n2 = 2 * plan.bpad
-        k_cols_ready()
-        sw_all = _sw(ws.k_rows, ws.k_cols, None)
-        peers = [(rank + 1 + k) % world for k in range(npairs)]
-        opp = (rank + world // 2) % world if world % 2 == 0 else None    # the antipodal rank (at 2 ranks: the other rank)
-        if save_remote:
-            ws.saved_blocks, ws.recompute_ranges = [], []
-        if npairs:
-            outbox, inbox, in_split, out_split, out_row = _pair_exchange_buffers(dev, group, stream, world, rank, n2, npairs)
-        # One launch per peer when the operands arrive peer by peer (p2p_each) and the workspace has a launch group for each
-        # (local + peers + antipode + received <= 8); otherwise ONE launch over the whole pair range behind one wait.
-        per_peer = npairs > 0 and gather.mode == "p2p_each" and npairs + 3 <= nat.LAUNCH_GROUPS
-        group_of = 1
-        if npairs and per_peer:
-            for k, peer in enumerate(peers):
-                gather.wait_peer(peer)
-                cs = outbox[out_row[peer]]
-                if save_remote:
-                    st = _alloc_rect_stash(lib.crossclr_rect_stash_bytes(pp, 1), dev)
-                    nat.check(lib.crossclr_forward_rect_save(pp, _ptr(ws.xhat), _ptr(ws.xcols), peer, 1, 1, ws.temperature, ws.negative_w,
-                                                             sw_all, _ptr(part), group_of * plan.fwd_slots, _ptr(cs), _ptr(st), stream))
-                    ws.saved_blocks.append((peer, 1, st))
-                else:
-                    nat.check(lib.crossclr_forward_pairs(pp, _ptr(ws.xhat), _ptr(ws.xcols), peer, 1, ws.temperature, ws.negative_w,
-                                                         sw_all, _ptr(part), group_of * plan.fwd_slots, _ptr(cs), stream))
-                group_of += 1
-        elif npairs:
-            gather.wait_forward()   # (p2p: the peers this rank evaluates itself; all-gather: everything)
-            for peer in peers:      # (p2p_each beyond the workspace's launch groups: the slices arrive one by one, the launch needs all)
-                gather.wait_peer(peer)
-            colsum = torch.empty(npairs * n2, **f32)
-            if save_remote:
-                st = _alloc_rect_stash(lib.crossclr_rect_stash_bytes(pp, npairs), dev)
-                nat.check(lib.crossclr_forward_rect_save(pp, _ptr(ws.xhat), _ptr(ws.xcols), peers[0], npairs, 1, ws.temperature,
-                                                         ws.negative_w, sw_all, _ptr(part), plan.fwd_slots, _ptr(colsum), _ptr(st), stream))
-                ws.saved_blocks.append((peers[0], npairs, st))
-            else:
-                nat.check(lib.crossclr_forward_pairs(pp, _ptr(ws.xhat), _ptr(ws.xcols), peers[0], npairs, ws.temperature,
-                                                     ws.negative_w, sw_all, _ptr(part), plan.fwd_slots, _ptr(colsum), stream))
-            # the outbox rows are ordered by peer rank (the all-to-all's order), the launch's by distance: one small copy per peer
-            cv = colsum.view(npairs, n2)
-            for k, peer in enumerate(peers):
-                outbox[out_row[peer]].copy_(cv[k])
-            group_of = 2
-        if save_remote and npairs:
-            if partner_possible:
-                ws.partner_peers = peers        # the backward ships these blocks' transposed contributions instead
-            else:
-                ws.recompute_ranges.append(((rank - npairs) % world, npairs))
-        if opp is not None:   # both sides evaluate their own rows of the antipodal block
-            gather.wait_peer(opp)
-            if save_remote:
-                st = _alloc_rect_stash(lib.crossclr_rect_stash_bytes(pp, 1), dev)
-                nat.check(lib.crossclr_forward_rect_save(pp, _ptr(ws.xhat), _ptr(ws.xcols), opp, 1, 0, ws.temperature, ws.negative_w,
-                                                         sw_all, _ptr(part), group_of * plan.fwd_slots, None, _ptr(st), stream))
-                ws.saved_blocks.append((opp, 1, st))
-            else:
-                sw_opp = None
-                if ws.k_rows is not None:
-                    sw_opp = ctypes.pointer(nat.SampleWeights(ws.k_rows.data_ptr(), ws.k_cols.data_ptr() + 4 * opp * n2, 0))
-                nat.check(lib.crossclr_forward_w(pp, _ptr(ws.xhat), ctypes.c_void_p(ws.xcols.data_ptr() + opp * plan.operand_bytes),
-                                                 1, opp, -1, ws.temperature, ws.negative_w, sw_opp, _ptr(part),
-                                                 group_of * plan.fwd_slots, stream))
-            group_of += 1
-        if npairs:
-            # ship the column sums of block (r, s) to rank s: ONE all-to-all that moves exactly the rows somebody is owed
-            # (npairs x 2 bpad floats out, as many in; the received rows are added in rank order: deterministic)
-            dist.all_to_all_single(inbox.view(-1), outbox.view(-1), output_split_sizes=out_split, input_split_sizes=in_split, group=group)
-            received = inbox.sum(0) if npairs > 1 else inbox[0]     # (kept in a variable: _ptr is a bare address)
-            nat.check(lib.crossclr_forward_add(pp, _ptr(part), group_of * plan.fwd_slots, _ptr(received), stream))
-            group_of += 1
-        nlaunch = group_of
-    elif sharded:
-        gather.wait()
-        k_cols_ready()
-        # wide bf16 plans (D > 1024) with a backward to follow: the block against the other world - 1 ranks saves its bf16 records too (the
-        # generic forward in the rectangular layout the D-slice backward reads: 0.5 GiB per rank-block at b = 8192);
-        # exact-fp32 plans with a backward to follow: the block against the other world - 1 ranks saves its fp32 exponentials too
-        # (crossclr_forward_rect_save / crossclr_backward_rect_saved on the generic kernels: 1 GiB per rank-block at b = 8192), so that
-        # the backward of the remote blocks is the gradient product alone (2.3 instead of 6.8 ms per 8192^2 block)
-        rect_bytes = 0
-        if ((mode == nat.MODE_FP32 or plan.Dpad > 1024) and world >= 2 and ws.stash is not None and stash_everywhere and
-                os.environ.get("CROSSCLR_DISABLE_REMOTE_SAVE") != "1"):
-            rect_bytes = int(lib.crossclr_rect_stash_bytes(pp, world - 1))
-        st_r = _alloc_stash(rect_bytes, dev) if rect_bytes > 0 else None
-        if st_r is not None:
-            first = (rank + 1) % world
-            nat.check(lib.crossclr_forward_rect_save(pp, _ptr(ws.xhat), _ptr(ws.xcols), first, world - 1, 0, ws.temperature, ws.negative_w,
-                                                     _sw(ws.k_rows, ws.k_cols, None), _ptr(part), plan.fwd_slots, None, _ptr(st_r), stream))
-            ws.saved_blocks, ws.recompute_ranges = [(first, world - 1, st_r)], []
-        else:
-            nat.check(lib.crossclr_forward_w(pp, _ptr(ws.xhat), _ptr(ws.xcols), world, 0, rank, ws.temperature,
-                                             ws.negative_w, _sw(ws.k_rows, ws.k_cols, None), _ptr(part), plan.fwd_slots, stream))
-    with _Range("crossclr.forward_finish"):
-        nat.check(lib.crossclr_forward_finish_w(pp, _ptr(part), nlaunch * plan.fwd_slots, _ptr(ws.diag), ws.temperature,
-                                                ws.negative_w, _sw(ws.k_rows, ws.k_rows, ws.lw), _ptr(ws.logz), _ptr(ws.rz),
-                                                _ptr(ws.wrz), _ptr(ws.loss_sum), stream))
-    if sharded:
-        # the backward's remote launch needs every rank's omega/Z: gathered asynchronously, waited for in the backward
-        # (w * omega/Z of the columns is recomputed there: the same fp32 product the finish kernel forms).  Only when a
-        # backward will follow: under no_grad nobody would ever wait for the collective or keep its buffer alive.
-        ws.rz_cols, ws.wrz_cols, ws.stats_work = None, None, None
-        if save_for_backward:
-            ws.rz_cols = torch.empty(world * ws.rz.numel(), **f32)
-            ws.stats_work = dist.all_gather_into_tensor(ws.rz_cols, ws.rz, group=group, async_op=True)
-        total = ws.loss_sum[:1].clone()
-        dist.all_reduce(total, group=group)
-        loss = (total / (2.0 * b * world)).reshape(())
-        if not save_for_backward and ws.exchange is not None:
-            ws.exchange.wait()     # nobody will wait later: the late slices' sends / receives must not outlive their buffers
-        elif partner_possible and ws.partner_peers is not None:
-            ws.exchange.finish()   # (deferred late slices are never requested in this scheme)
-    else:
-        ws.rz_cols, ws.wrz_cols, ws.stats_work = ws.rz, ws.wrz, None
-        loss = ws.loss_sum[1]      # = sum / (2 B), written by the finish kernel (a 0-dim view of the 8-byte-per-block loss buffer)
-    return loss, ws
 
 
-def _forward_row_shift(lib, ws, part, gather, group, stream, b, world, rank, dev, needs_backward, k_cols_ready):
-    """Two-pass forward (include/crossclr.h, "two-pass soft-max"): row maxima, then sums relative to them.
-    k_cols_ready: waits for the asynchronous gather of the other ranks' negative scales (ws.k_cols) -- every launch over the
-    gathered operand reads them, here and in the backward (`gather.wait()` covers the operand exchange only)."""
+# Pair evaluation (bf16 register-resident path, >= 3 ranks): the (r, s) block of the symmetric matrix of exponentials
+# is evaluated by ONE of the two ranks, which ships its column sums to the other -- 3 instead of 7 remote blocks at
+# 8 ranks (+ the antipodal one, evaluated by both).  Also the 2-rank run whose one remote block saves its exponentials: no pairs,
+# the antipode alone.  Returns the number of launch groups the finish kernel adds up (local block included).
+def _forward_pair_blocks(ws, scheme, part, stream, save_remote: bool) -> int:
     import torch.distributed as dist
-    plan = ws.plan
-    pp = ctypes.byref(plan)
+    (lib, plan, pp), dev = _abi(ws), part.device
+    rank, world, gather = ws.rank, ws.world, ws.exchange
+    npairs, peers, opp = scheme.npairs, scheme.peers, scheme.opp
+    T, w = ws.temperature, ws.negative_w
+    n2 = 2 * plan.bpad
+    _k_cols_ready(ws)
+    sw_all = _sw(ws.k_rows, ws.k_cols, None)
+    if save_remote:
+        ws.saved_blocks, ws.recompute_ranges = [], []
+    if npairs:
+        outbox, inbox, in_split, out_split, out_row = _pair_exchange_buffers(dev, ws.group, stream, world, rank, n2, npairs)
+    # One launch per peer when the operands arrive peer by peer (p2p_each) and the workspace has a launch group for each
+    # (local + peers + antipode + received <= 8); otherwise ONE launch over the whole pair range behind one wait.
+    per_peer = npairs > 0 and gather.mode == "p2p_each" and npairs + 3 <= nat.LAUNCH_GROUPS
+    launches = []               # (first rank, ranks, where the block's column sums go)
+    if per_peer:
+        launches = [(peer, 1, outbox[out_row[peer]]) for peer in peers]
+    elif npairs:
+        colsum = torch.empty(npairs * n2, dtype=torch.float32, device=dev)
+        launches = [(peers[0], npairs, colsum)]
+        gather.wait_forward()   # (p2p: the peers this rank evaluates itself; all-gather: everything)
+    group_of = 1
+    for first, n, cs in launches:
+        for k in range(n):      # (p2p_each beyond the workspace's launch groups: the slices arrive one by one, the launch needs all)
+            gather.wait_peer((first + k) % world)
+        if save_remote:
+            st = _alloc_rect_stash(lib.crossclr_rect_stash_bytes(pp, n), dev)
+            nat.check(lib.crossclr_forward_rect_save(pp, _ptr(ws.xhat), _ptr(ws.xcols), first, n, 1, T, w,
+                                                     sw_all, _ptr(part), group_of * plan.fwd_slots, _ptr(cs), _ptr(st), stream))
+            ws.saved_blocks.append((first, n, st))
+        else:
+            nat.check(lib.crossclr_forward_pairs(pp, _ptr(ws.xhat), _ptr(ws.xcols), first, n, T, w,
+                                                 sw_all, _ptr(part), group_of * plan.fwd_slots, _ptr(cs), stream))
+        group_of += 1
+    if npairs and not per_peer:
+        # the outbox rows are ordered by peer rank (the all-to-all's order), the launch's by distance: one small copy per peer
+        cv = colsum.view(npairs, n2)
+        for k, peer in enumerate(peers):
+            outbox[out_row[peer]].copy_(cv[k])
+    if save_remote and npairs:
+        if scheme.partner_possible:
+            ws.partner_peers = list(peers)        # the backward ships these blocks' transposed contributions instead
+        else:
+            ws.recompute_ranges.append(((rank - npairs) % world, npairs))
+    if opp is not None:   # both sides evaluate their own rows of the antipodal block
+        gather.wait_peer(opp)
+        if save_remote:
+            st = _alloc_rect_stash(lib.crossclr_rect_stash_bytes(pp, 1), dev)
+            nat.check(lib.crossclr_forward_rect_save(pp, _ptr(ws.xhat), _ptr(ws.xcols), opp, 1, 0, T, w,
+                                                     sw_all, _ptr(part), group_of * plan.fwd_slots, None, _ptr(st), stream))
+            ws.saved_blocks.append((opp, 1, st))
+        else:
+            sw_opp = None
+            if ws.k_rows is not None:
+                sw_opp = ctypes.pointer(nat.SampleWeights(ws.k_rows.data_ptr(), ws.k_cols.data_ptr() + 4 * opp * n2, 0))
+            nat.check(lib.crossclr_forward_w(pp, _ptr(ws.xhat), ctypes.c_void_p(ws.xcols.data_ptr() + opp * plan.operand_bytes), 1, opp, -1, T, w,
+                                             sw_opp, _ptr(part), group_of * plan.fwd_slots, stream))
+        group_of += 1
+    if npairs:
+        # ship the column sums of block (r, s) to rank s: ONE all-to-all that moves exactly the rows somebody is owed
+        # (npairs x 2 bpad floats out, as many in; the received rows are added in rank order: deterministic)
+        dist.all_to_all_single(inbox.view(-1), outbox.view(-1), output_split_sizes=out_split, input_split_sizes=in_split, group=ws.group)
+        received = inbox.sum(0) if npairs > 1 else inbox[0]     # (kept in a variable: _ptr is a bare address)
+        nat.check(lib.crossclr_forward_add(pp, _ptr(part), group_of * plan.fwd_slots, _ptr(received), stream))
+        group_of += 1
+    return group_of
+
+
+# ONE launch over the block against all other ranks (behind the whole exchange); 2 launch groups with the local block
+def _forward_all_remote(ws, scheme, part, stream) -> int:
+    lib, plan, pp = _abi(ws)
+    rank, world = ws.rank, ws.world
+    ws.exchange.wait()
+    _k_cols_ready(ws)
+    # wide bf16 plans (D > 1024) with a backward to follow: the block against the other world - 1 ranks saves its bf16 records too (the
+    # generic forward in the rectangular layout the D-slice backward reads: 0.5 GiB per rank-block at b = 8192);
+    # exact-fp32 plans with a backward to follow: the block against the other world - 1 ranks saves its fp32 exponentials too
+    # (crossclr_forward_rect_save / crossclr_backward_rect_saved on the generic kernels: 1 GiB per rank-block at b = 8192), so that
+    # the backward of the remote blocks is the gradient product alone (2.3 instead of 6.8 ms per 8192^2 block)
+    st_r = None
+    if scheme.save_all_remote and ws.stash is not None:
+        st_r = _alloc_stash(int(lib.crossclr_rect_stash_bytes(pp, world - 1)), part.device)
+    if st_r is not None:
+        first = (rank + 1) % world
+        nat.check(lib.crossclr_forward_rect_save(pp, _ptr(ws.xhat), _ptr(ws.xcols), first, world - 1, 0, ws.temperature, ws.negative_w,
+                                                 _sw(ws.k_rows, ws.k_cols, None), _ptr(part), plan.fwd_slots, None, _ptr(st_r), stream))
+        ws.saved_blocks, ws.recompute_ranges = [(first, world - 1, st_r)], []
+    else:
+        nat.check(lib.crossclr_forward_w(pp, _ptr(ws.xhat), _ptr(ws.xcols), world, 0, rank, ws.temperature,
+                                         ws.negative_w, _sw(ws.k_rows, ws.k_cols, None), _ptr(part), plan.fwd_slots, stream))
+    return 2
+
+
+def _forward_row_shift(ws, scheme, part, stream) -> int:
+    """Two-pass forward (include/crossclr.h, "two-pass soft-max"): row maxima, then sums relative to them.  Returns the number of launch
+    groups for the finish kernel."""
+    import torch.distributed as dist
+    (lib, plan, pp), dev = _abi(ws), part.device
+    rank, world = ws.rank, ws.world
     f32 = dict(dtype=torch.float32, device=dev)
     ws.stash = None
     ws.shift = torch.empty(2 * plan.bpad, **f32)
     sw_loc, sw_all = _sw(ws.k_rows, ws.k_rows, None), _sw(ws.k_rows, ws.k_cols, None)
     T, w = ws.temperature, ws.negative_w
-    nat.check(lib.crossclr_forward_rowmax(pp, _ptr(ws.xhat), _ptr(ws.xhat), 1, rank, -1, T, w, sw_loc, _ptr(part), _ptr(ws.shift), 0,
-                                          stream))
+    nat.check(lib.crossclr_forward_rowmax(pp, _ptr(ws.xhat), _ptr(ws.xhat), 1, rank, -1, T, w, sw_loc, _ptr(part), _ptr(ws.shift), 0, stream))
     if ws.sharded:
-        gather.wait()
-        k_cols_ready()
-        nat.check(lib.crossclr_forward_rowmax(pp, _ptr(ws.xhat), _ptr(ws.xcols), world, 0, rank, T, w, sw_all, _ptr(part),
-                                              _ptr(ws.shift), 1, stream))
+        ws.exchange.wait()
+        _k_cols_ready(ws)
+        nat.check(lib.crossclr_forward_rowmax(pp, _ptr(ws.xhat), _ptr(ws.xcols), world, 0, rank, T, w, sw_all, _ptr(part), _ptr(ws.shift), 1, stream))
     # sharded run with a backward to follow (exact-fp32 plans: fp32 fragments; bf16 register-resident plans: bf16 records): the block against
     # the other world - 1 ranks saves U AND Ut (relative to the remote rows' shifts), so the ranks exchange their row maxima HERE, between the passes (2 bpad floats per rank; every rank takes this
     # branch or none: the condition reads the plan and the environment only).  The backward then recomputes nothing at any temperature.
-    ws.saved_blocks, ws.recompute_ranges = None, None
     shift_all = None
-    if (ws.sharded and needs_backward and os.environ.get("CROSSCLR_DISABLE_REMOTE_SAVE") != "1" and
-            int(lib.crossclr_rect_stash_bytes_s(pp, world - 1)) > 0 and int(lib.crossclr_stash_bytes_s(pp)) > 0):
+    if scheme.exchange_shifts:
         shift_all = torch.empty(world * ws.shift.numel(), **f32)
-        dist.all_gather_into_tensor(shift_all, ws.shift, group=group)
+        dist.all_gather_into_tensor(shift_all, ws.shift, group=ws.group)
     # second pass over the local block; with a backward to follow (exact-fp32 plans) it also saves the exponentials relative to the
     # row's and to the column's shift, and the backward does not recompute the similarity product
-    ws.stash = _alloc_stash(lib.crossclr_stash_bytes_s(pp), dev) if needs_backward else None
+    ws.stash = _alloc_stash(lib.crossclr_stash_bytes_s(pp), dev) if scheme.save else None
     if ws.stash is not None:
         nat.check(lib.crossclr_forward_save_s(pp, _ptr(ws.xhat), T, w, sw_loc, _ptr(ws.shift), _ptr(part), 0, _ptr(ws.stash), stream))
     else:
         nat.check(lib.crossclr_forward_s(pp, _ptr(ws.xhat), _ptr(ws.xhat), 1, rank, -1, T, w, sw_loc, _ptr(ws.shift), _ptr(part), 0, stream))
-    nlaunch = 1
-    if ws.sharded:
-        st_r = None
-        if shift_all is not None and ws.stash is not None:
-            st_r = _alloc_stash(int(lib.crossclr_rect_stash_bytes_s(pp, world - 1)), dev)
-        if st_r is not None:
-            first = (rank + 1) % world
-            nat.check(lib.crossclr_forward_rect_save_s(pp, _ptr(ws.xhat), _ptr(ws.xcols), first, world - 1, T, w, sw_all, _ptr(ws.shift),
-                                                       _ptr(shift_all), _ptr(part), plan.fwd_slots, _ptr(st_r), stream))
-            ws.saved_blocks = [(first, world - 1, st_r)]
-        else:
-            nat.check(lib.crossclr_forward_s(pp, _ptr(ws.xhat), _ptr(ws.xcols), world, 0, rank, T, w, sw_all, _ptr(ws.shift), _ptr(part),
-                                             plan.fwd_slots, stream))
-        nlaunch = 2
-    nat.check(lib.crossclr_forward_finish_s(pp, _ptr(part), nlaunch * plan.fwd_slots, _ptr(ws.diag), T, w,
-                                            _sw(ws.k_rows, ws.k_rows, ws.lw), _ptr(ws.shift), _ptr(ws.logz), _ptr(ws.rz), _ptr(ws.wrz),
-                                            _ptr(ws.loss_sum), stream))
-    if ws.sharded:
-        # the remote backward needs every rank's omega/Z' AND the shifts they are relative to: one gather of both
-        ws.rz_cols, ws.wrz_cols, ws.shift_cols, ws.stats_work = None, None, None, None
-        if needs_backward:
-            both = torch.cat([ws.rz, ws.shift])
-            gathered = torch.empty(world * both.numel(), **f32)
-            ws.stats_work = dist.all_gather_into_tensor(gathered, both, group=group, async_op=True)
-            ws.rz_cols = gathered   # split after the wait, in the backward
-        total = ws.loss_sum[:1].clone()
-        dist.all_reduce(total, group=group)
-        loss = (total / (2.0 * b * world)).reshape(())
+    if not ws.sharded:
+        return 1
+    st_r = None
+    if shift_all is not None and ws.stash is not None:
+        st_r = _alloc_stash(int(lib.crossclr_rect_stash_bytes_s(pp, world - 1)), dev)
+    if st_r is not None:
+        first = (rank + 1) % world
+        nat.check(lib.crossclr_forward_rect_save_s(pp, _ptr(ws.xhat), _ptr(ws.xcols), first, world - 1, T, w, sw_all, _ptr(ws.shift),
+                                                   _ptr(shift_all), _ptr(part), plan.fwd_slots, _ptr(st_r), stream))
+        ws.saved_blocks = [(first, world - 1, st_r)]
     else:
+        nat.check(lib.crossclr_forward_s(pp, _ptr(ws.xhat), _ptr(ws.xcols), world, 0, rank, T, w, sw_all, _ptr(ws.shift), _ptr(part),
+                                         plan.fwd_slots, stream))
+    return 2
+
+
+# The finish kernel over the launch groups' partial sums, the loss all-reduce, the statistics gather for the backward (both regimes: the
+# two-pass one hands its shifts to the finish kernel and gathers them along with the statistics).  Returns the loss.
+def _forward_finish(ws, scheme, part, nlaunch: int, stream) -> torch.Tensor:
+    import torch.distributed as dist
+    lib, plan, pp = _abi(ws)
+    sw = _sw(ws.k_rows, ws.k_rows, ws.lw)
+    if ws.shift is not None:
+        nat.check(lib.crossclr_forward_finish_s(pp, _ptr(part), nlaunch * plan.fwd_slots, _ptr(ws.diag), ws.temperature, ws.negative_w, sw,
+                                                _ptr(ws.shift), _ptr(ws.logz), _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.loss_sum), stream))
+    else:
+        with _Range("crossclr.forward_finish"):
+            nat.check(lib.crossclr_forward_finish_w(pp, _ptr(part), nlaunch * plan.fwd_slots, _ptr(ws.diag), ws.temperature, ws.negative_w, sw,
+                                                    _ptr(ws.logz), _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.loss_sum), stream))
+    if not ws.sharded:
         ws.rz_cols, ws.wrz_cols, ws.shift_cols, ws.stats_work = ws.rz, ws.wrz, ws.shift, None
-        loss = ws.loss_sum[1]
-    return loss, ws
+        return ws.loss_sum[1]      # = sum / (2 B), written by the finish kernel (a 0-dim view of the 8-byte-per-block loss buffer)
+    # the backward's remote launch needs every rank's omega/Z (two-pass regime: omega/Z' AND the shifts they are relative to: one gather of
+    # both, split after the wait, in the backward): gathered asynchronously, waited for in the backward
+    # (w * omega/Z of the columns is recomputed there: the same fp32 product the finish kernel forms).  Only when a
+    # backward will follow: under no_grad nobody would ever wait for the collective or keep its buffer alive.
+    ws.rz_cols, ws.wrz_cols, ws.shift_cols, ws.stats_work = None, None, None, None
+    if scheme.save:
+        mine = ws.rz if ws.shift is None else torch.cat([ws.rz, ws.shift])
+        ws.rz_cols = torch.empty(ws.world * mine.numel(), dtype=torch.float32, device=part.device)
+        ws.stats_work = dist.all_gather_into_tensor(ws.rz_cols, mine, group=ws.group, async_op=True)
+    total = ws.loss_sum[:1].clone()
+    dist.all_reduce(total, group=ws.group)
+    loss = (total / (2.0 * plan.b * ws.world)).reshape(())
+    if not scheme.save and ws.exchange is not None:
+        ws.exchange.wait()     # nobody will wait later: the late slices' sends / receives must not outlive their buffers
+    elif scheme.partner_possible and ws.partner_peers is not None:
+        ws.exchange.finish()   # (deferred late slices are never requested in this scheme)
+    return loss
 
 
-def _xf_selftest_remote(dev, D: int, weighted: bool, launches: int = 2):
+def _xf_selftest_remote(dev, D: int, weighted: bool, entry_name: str = _XF_REMOTE, launches: int = 2):
     """The pair kernel's RECTANGULAR and TRANSPOSED instantiations (crossclr_backward_rect_saved_xfp / _t_xfp: separate template modes with their
     own hand-counted waits) against the LDS-staged crossclr_backward_rect_saved / _t over the same saved exponentials, bit for bit: rank 1 of a
     synthetic 3-rank run (384 rows per rank: one pair block, wrap-around of the rank segments).  True / False, None when there is nothing to
-    compare on this build."""
+    compare on this build.  (`entry_name`: the gate's signature; both instantiations are always compared, under the one name.)"""
     lib = nat.library()
     stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
     world, rank, b = 3, 1, 384
@@ -1090,9 +1150,7 @@ def _xf_selftest_remote(dev, D: int, weighted: bool, launches: int = 2):
     xf_all = torch.empty(world * plan.operand_bytes, dtype=torch.uint8, device=dev)
     inv, diag = torch.empty(n2, **f32), torch.empty(plan.bpad, **f32)
     for r in range(world):
-        v = torch.randn(b, D, generator=g)
-        t = (v + 0.5 * torch.randn(b, D, generator=g)).to(dev)
-        v = v.to(dev)
+        v, t = _aligned_pair(b, D, g, dev)
         nat.check(lib.crossclr_normalize(pp, _ptr(v), _ptr(t), v.stride(0), t.stride(0), nat.IN_F32, xall.data_ptr() + r * plan.operand_bytes,
                                          _ptr(inv), _ptr(diag), stream))
     nat.check(lib.crossclr_pack_xf_from_packed(pp, _ptr(xall), world, _ptr(xf_all), stream))
@@ -1145,153 +1203,157 @@ def _remote_xfp(ws, plan, lib, pp, dev) -> bool:
     if _saved_backward_entry(ws, plan, dev) != "crossclr_backward_saved_xfp":
         return False
     # the rectangular and transposed instantiations are verified on their own (round-4 review: the local block's self-test says nothing about them)
-    weighted = ws.k_rows is not None
-    key = (str(dev), plan.Dpad, weighted, "crossclr_backward_rect_saved_xfp", nat.library_path())
-    ok = _xf_verified.get(key)
-    if ok is None:
-        if nat.injected_for_testing():
-            ok = True
-        elif dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            return False
-        else:
-            verdict = _xf_selftest_remote(dev, plan.D, weighted)
-            if verdict is False:
-                warnings.warn(f"CrossCLR: crossclr_backward_rect_saved_xfp / _t_xfp disagree with the LDS-staged kernels on this device / build at "
-                              f"Dpad = {plan.Dpad}; remote blocks keep the LDS-staged kernels in this process")
-            ok = bool(verdict)
-        _xf_verified[key] = ok
-    return ok
+    return bool(_xf_gate(dev, plan, ws.k_rows is not None, _XF_REMOTE, _xf_selftest_remote))
+
+
+# Every rank's omega/Z (ws.rz_cols) has landed and w * omega/Z (ws.wrz_cols) is formed; two-pass regime: the shifts that came along are split off
+def _col_stats_ready(ws) -> None:
+    if ws.wrz_cols is not None:
+        return
+    if ws.shift is not None:
+        ws.stats_work.wait()
+        both = ws.rz_cols.view(ws.world, 2, -1)
+        ws.rz_cols = both[:, 0].contiguous().view(-1)
+        ws.shift_cols = both[:, 1].contiguous().view(-1)
+    else:
+        _traced_wait("statistics", [ws.stats_work])
+    ws.wrz_cols = ws.rz_cols * ws.negative_w
+
+
+def _backward_two_pass(ws, gbuf, stream) -> None:   # two-pass (small temperature) regime: generic kernels with per-row shifts
+    lib, plan, pp = _abi(ws)
+    rank, world = ws.rank, ws.world
+    if ws.stash is not None:
+        nat.check(lib.crossclr_backward_saved_s(pp, _ptr(ws.xhat), _ptr(ws.stash), ws.temperature, ws.negative_w, _ptr(ws.rz),
+                                                _ptr(ws.wrz), _sw(ws.k_rows, ws.k_rows, None), _ptr(gbuf), 0, stream))
+        ws.stash = None
+    else:
+        nat.check(lib.crossclr_backward_s(pp, _ptr(ws.xhat), _ptr(ws.xhat), 1, rank, -1, ws.temperature, ws.negative_w,
+                                          _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.rz), _ptr(ws.wrz), _sw(ws.k_rows, ws.k_rows, None),
+                                          _ptr(ws.shift), _ptr(ws.shift), _ptr(gbuf), 0, stream))
+    if not ws.sharded:
+        return
+    _col_stats_ready(ws)
+    if ws.saved_blocks:   # exact-fp32 plans: U and Ut of the block against the other ranks were saved (crossclr_forward_rect_save_s)
+        for first, n, st in ws.saved_blocks:
+            nat.check(lib.crossclr_backward_rect_saved_s(pp, _ptr(ws.xcols), _ptr(st), first, n, ws.temperature, ws.negative_w,
+                                                         _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.rz_cols), _ptr(ws.wrz_cols),
+                                                         _sw(ws.k_rows, ws.k_cols, None), _ptr(gbuf), 1, stream))
+        ws.saved_blocks = None
+    else:
+        nat.check(lib.crossclr_backward_s(pp, _ptr(ws.xhat), _ptr(ws.xcols), world, 0, rank, ws.temperature, ws.negative_w,
+                                          _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.rz_cols), _ptr(ws.wrz_cols),
+                                          _sw(ws.k_rows, ws.k_cols, None), _ptr(ws.shift), _ptr(ws.shift_cols), _ptr(gbuf), 1, stream))
+
+
+def _backward_local(ws, gbuf, stream) -> None:      # the local block: from the saved exponentials when the forward saved them, recomputed otherwise
+    lib, plan, pp = _abi(ws)
+    if ws.stash is None:
+        # (column statistics of the local block = this rank's row statistics)
+        nat.check(lib.crossclr_backward_w(pp, _ptr(ws.xhat), _ptr(ws.xhat), 1, ws.rank, -1, ws.temperature, ws.negative_w, _ptr(ws.rz), _ptr(ws.wrz),
+                                          _ptr(ws.rz), _ptr(ws.wrz), _sw(ws.k_rows, ws.k_rows, None), _ptr(gbuf), 0, stream))
+        return
+    with _Range("crossclr.backward"):
+        entry = _saved_backward_entry(ws, plan, gbuf.device)
+        operand = ws.xhat if entry == "crossclr_backward_saved" else ws.xf
+        nat.check(getattr(lib, entry)(pp, _ptr(operand), _ptr(ws.stash), ws.temperature, ws.negative_w, _ptr(ws.rz), _ptr(ws.wrz),
+                                      _sw(ws.k_rows, ws.k_rows, None), _ptr(gbuf), 0, stream))
+    ws.stash = None   # consumed: give the 0.27 GB back to the allocator as soon as the launch is queued
+    if not (ws.sharded and ws.saved_blocks is not None):
+        ws.xf = None      # (a sharded step's partner gradients read it once more below)
+
+
+# The remote blocks this rank evaluated in the forward, from their saved exponentials; the pair partners' blocks: partner gradients or recompute
+def _backward_saved_remote(ws, gbuf, stream) -> None:
+    (lib, plan, pp), dev = _abi(ws), gbuf.device
+    rank, world = ws.rank, ws.world
+    _col_stats_ready(ws)
+    sw_all = _sw(ws.k_rows, ws.k_cols, None)
+    partner_work = None
+    # remote blocks on the fragment-major operand: the slices this rank received are re-laid out HERE (the exchange moved the row-major
+    # operand once; crossclr_pack_xf_from_packed: the slices of the blocks this rank evaluated, ~40 us for 117 MB at 8 ranks), the
+    # transposes read this rank's own copy
+    remote_xfp = _remote_xfp(ws, plan, lib, pp, dev)
+    if remote_xfp:
+        ws.xf_all = torch.empty(world * plan.operand_bytes, dtype=torch.uint8, device=dev)
+        for first, n, _ in ws.saved_blocks:
+            runs = [(first, min(n, world - first))] + ([(0, n - (world - first))] if first + n > world else [])
+            for r0, cnt in runs:
+                nat.check(lib.crossclr_pack_xf_from_packed(pp, ws.xcols.data_ptr() + r0 * plan.operand_bytes, cnt,
+                                                           ws.xf_all.data_ptr() + r0 * plan.operand_bytes, stream))
+    if ws.partner_peers:
+        # Pair blocks, the partner's half first (its transfer then hides behind this rank's own blocks): block (r, s) transposed,
+        # from the exponentials saved for it -> [2 bpad, Dpad] fp32 per partner, shipped with one all-to-all.
+        import torch.distributed as dist
+        n2, npairs = 2 * plan.bpad, len(ws.partner_peers)
+        nel = n2 * plan.Dpad
+        _, _, in_split, out_split, out_row = _pair_exchange_buffers(dev, ws.group, stream, world, rank, n2, npairs)
+        outg, ing, tmp = _partner_gradient_buffers(dev, ws.group, stream, npairs, nel, plan.gbuf_bytes // 4)
+        for first, n, st in ws.saved_blocks:
+            for which in range(n):
+                peer = (first + which) % world
+                if peer not in out_row or peer not in ws.partner_peers:
+                    continue                                # (the antipodal block: both sides own their rows)
+                entry_t, operand_t = ((lib.crossclr_backward_rect_saved_t_xfp, ws.xf) if remote_xfp else
+                                      (lib.crossclr_backward_rect_saved_t, ws.xhat))
+                nat.check(entry_t(pp, _ptr(operand_t), _ptr(st), first, n, which, ws.temperature, ws.negative_w,
+                                  _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.rz_cols), _ptr(ws.wrz_cols), sw_all, _ptr(tmp), stream))
+                torch.sum(tmp.view(-1, nel), 0, out=outg[out_row[peer]])      # the column slices, in index order
+        partner_work = dist.all_to_all_single(ing.view(-1), outg.view(-1), output_split_sizes=[x * plan.Dpad for x in out_split],
+                                              input_split_sizes=[x * plan.Dpad for x in in_split], group=ws.group, async_op=True)
+    for first, n, st in ws.saved_blocks:        # blocks this rank evaluated in the forward: from their saved exponentials
+        entry_r, operand_r = ((lib.crossclr_backward_rect_saved_xfp, ws.xf_all) if remote_xfp else
+                              (lib.crossclr_backward_rect_saved, ws.xcols))
+        nat.check(entry_r(pp, _ptr(operand_r), _ptr(st), first, n, ws.temperature, ws.negative_w,
+                          _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.rz_cols), _ptr(ws.wrz_cols), sw_all, _ptr(gbuf), 1, stream))
+    if ws.recompute_ranges:
+        ws.exchange.wait()                      # (point-to-point exchange: the slices only this recompute needs)
+    for first, n in ws.recompute_ranges:        # blocks the other side of a pair evaluated: recompute
+        nat.check(lib.crossclr_backward_ranks(pp, _ptr(ws.xhat), _ptr(ws.xcols), first, n, ws.temperature, ws.negative_w, _ptr(ws.rz), _ptr(ws.wrz),
+                                              _ptr(ws.rz_cols), _ptr(ws.wrz_cols), sw_all, _ptr(gbuf), 1, stream))
+    if partner_work is not None:
+        _traced_wait("partner gradients", [partner_work])
+        g0 = gbuf[:nel]
+        for k in range(npairs):          # fixed order over the source ranks: deterministic
+            g0 += ing[k]
+    ws.saved_blocks = None
+    ws.xf = ws.xf_all = None
+
+
+# Nothing was saved for the remote blocks (or a first backward consumed it): ONE recomputing launch over every other rank's slice
+def _backward_recompute_remote(ws, gbuf, stream) -> None:
+    lib, plan = nat.library(), ws.plan
+    if ws.partner_peers is not None:
+        # Partner-gradient scheme (the default from 3 ranks): the first backward consumed the saved blocks, and the operand slices of
+        # the ranks whose blocks the PARTNER evaluated were never requested (deferred exchange) -- a recomputing launch over every
+        # rank's slice would read memory nobody wrote.  Every rank takes this branch together.
+        raise RuntimeError("CrossCLR (sharded, partner gradients): backward was called a second time through the same graph "
+                           "(retain_graph=True); the saved exponentials are released after the first backward and the late operand "
+                           "slices are never exchanged in this scheme -- run the forward again, or set CROSSCLR_PARTNER_GRADS=0 on "
+                           "every rank (the recomputing scheme supports repeated backwards)")
+    _col_stats_ready(ws)
+    if ws.exchange is not None:
+        ws.exchange.wait()     # this launch reads EVERY rank's slice of xcols: also the late point-to-point ones
+    nat.check(lib.crossclr_backward_w(ctypes.byref(plan), _ptr(ws.xhat), _ptr(ws.xcols), ws.world, 0, ws.rank, ws.temperature,
+                                      ws.negative_w, _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.rz_cols),
+                                      _ptr(ws.wrz_cols), _sw(ws.k_rows, ws.k_cols, None), _ptr(gbuf), 1, stream))
 
 
 def _backward_impl(ws: _Workspace, video: torch.Tensor, text: torch.Tensor, grad_out: torch.Tensor):
     if ws.step is not None and ws.prenormalized != 2:
         return _backward_step(ws, video, text, grad_out)
-    lib = nat.library()
-    plan = ws.plan
-    pp = ctypes.byref(plan)
-    dev = video.device
+    lib, plan, pp = _abi(ws)
     stream = _stream_for(video)
-    gbuf = torch.empty(plan.gbuf_bytes // 4, dtype=torch.float32, device=dev)
-    rank, world = ws.rank, ws.world
-    rz_loc, wrz_loc = ws.rz, ws.wrz   # column statistics of the local block = this rank's row statistics
-    if ws.shift is not None:   # two-pass (small temperature) regime: generic kernels with per-row shifts
-        if ws.stash is not None:
-            nat.check(lib.crossclr_backward_saved_s(pp, _ptr(ws.xhat), _ptr(ws.stash), ws.temperature, ws.negative_w, _ptr(ws.rz),
-                                                    _ptr(ws.wrz), _sw(ws.k_rows, ws.k_rows, None), _ptr(gbuf), 0, stream))
-            ws.stash = None
-        else:
-            nat.check(lib.crossclr_backward_s(pp, _ptr(ws.xhat), _ptr(ws.xhat), 1, rank, -1, ws.temperature, ws.negative_w,
-                                              _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.rz), _ptr(ws.wrz), _sw(ws.k_rows, ws.k_rows, None),
-                                              _ptr(ws.shift), _ptr(ws.shift), _ptr(gbuf), 0, stream))
-        if ws.sharded:
-            if ws.wrz_cols is None:
-                ws.stats_work.wait()
-                n2 = ws.rz.numel()
-                both = ws.rz_cols.view(world, 2, n2)
-                ws.rz_cols = both[:, 0].contiguous().view(-1)
-                ws.shift_cols = both[:, 1].contiguous().view(-1)
-                ws.wrz_cols = ws.rz_cols * ws.negative_w
-            if ws.saved_blocks:   # exact-fp32 plans: U and Ut of the block against the other ranks were saved (crossclr_forward_rect_save_s)
-                for first, n, st in ws.saved_blocks:
-                    nat.check(lib.crossclr_backward_rect_saved_s(pp, _ptr(ws.xcols), _ptr(st), first, n, ws.temperature, ws.negative_w,
-                                                                 _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.rz_cols), _ptr(ws.wrz_cols),
-                                                                 _sw(ws.k_rows, ws.k_cols, None), _ptr(gbuf), 1, stream))
-                ws.saved_blocks = None
-            else:
-                nat.check(lib.crossclr_backward_s(pp, _ptr(ws.xhat), _ptr(ws.xcols), world, 0, rank, ws.temperature, ws.negative_w,
-                                                  _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.rz_cols), _ptr(ws.wrz_cols),
-                                                  _sw(ws.k_rows, ws.k_cols, None), _ptr(ws.shift), _ptr(ws.shift_cols), _ptr(gbuf), 1, stream))
-    elif ws.stash is not None:
-        with _Range("crossclr.backward"):
-            entry = _saved_backward_entry(ws, plan, dev)
-            operand = ws.xhat if entry == "crossclr_backward_saved" else ws.xf
-            nat.check(getattr(lib, entry)(pp, _ptr(operand), _ptr(ws.stash), ws.temperature, ws.negative_w, _ptr(ws.rz), _ptr(ws.wrz),
-                                          _sw(ws.k_rows, ws.k_rows, None), _ptr(gbuf), 0, stream))
-        ws.stash = None   # consumed: give the 0.27 GB back to the allocator as soon as the launch is queued
-        if not (ws.sharded and ws.saved_blocks is not None):
-            ws.xf = None      # (a sharded step's partner gradients read it once more below)
+    gbuf = torch.empty(plan.gbuf_bytes // 4, dtype=torch.float32, device=video.device)
+    if ws.shift is not None:
+        _backward_two_pass(ws, gbuf, stream)
     else:
-        nat.check(lib.crossclr_backward_w(pp, _ptr(ws.xhat), _ptr(ws.xhat), 1, rank, -1, ws.temperature, ws.negative_w,
-                                          _ptr(ws.rz), _ptr(ws.wrz), _ptr(rz_loc), _ptr(wrz_loc),
-                                          _sw(ws.k_rows, ws.k_rows, None), _ptr(gbuf), 0, stream))
-    if ws.sharded and ws.shift is None and ws.saved_blocks is not None:
-        if ws.wrz_cols is None:
-            _traced_wait("statistics", [ws.stats_work])
-            ws.wrz_cols = ws.rz_cols * ws.negative_w
-        sw_all = _sw(ws.k_rows, ws.k_cols, None)
-        partner_work = None
-        # remote blocks on the fragment-major operand: the slices this rank received are re-laid out HERE (the exchange moved the row-major
-        # operand once; crossclr_pack_xf_from_packed: the slices of the blocks this rank evaluated, ~40 us for 117 MB at 8 ranks), the
-        # transposes read this rank's own copy
-        remote_xfp = _remote_xfp(ws, plan, lib, pp, dev)
-        if remote_xfp:
-            ws.xf_all = torch.empty(world * plan.operand_bytes, dtype=torch.uint8, device=dev)
-            for first, n, _ in ws.saved_blocks:
-                runs = [(first, min(n, world - first))] + ([(0, n - (world - first))] if first + n > world else [])
-                for r0, cnt in runs:
-                    nat.check(lib.crossclr_pack_xf_from_packed(pp, ws.xcols.data_ptr() + r0 * plan.operand_bytes, cnt,
-                                                               ws.xf_all.data_ptr() + r0 * plan.operand_bytes, stream))
-        if ws.partner_peers:
-            # Pair blocks, the partner's half first (its transfer then hides behind this rank's own blocks): block (r, s) transposed,
-            # from the exponentials saved for it -> [2 bpad, Dpad] fp32 per partner, shipped with one all-to-all.
-            import torch.distributed as dist
-            n2, npairs = 2 * plan.bpad, len(ws.partner_peers)
-            nel = n2 * plan.Dpad
-            _, _, in_split, out_split, out_row = _pair_exchange_buffers(dev, ws.group, stream, world, rank, n2, npairs)
-            outg, ing, tmp = _partner_gradient_buffers(dev, ws.group, stream, npairs, nel, plan.gbuf_bytes // 4)
-            for first, n, st in ws.saved_blocks:
-                for which in range(n):
-                    peer = (first + which) % world
-                    if peer not in out_row or peer not in ws.partner_peers:
-                        continue                                # (the antipodal block: both sides own their rows)
-                    entry_t, operand_t = ((lib.crossclr_backward_rect_saved_t_xfp, ws.xf) if remote_xfp else
-                                          (lib.crossclr_backward_rect_saved_t, ws.xhat))
-                    nat.check(entry_t(pp, _ptr(operand_t), _ptr(st), first, n, which, ws.temperature, ws.negative_w,
-                                      _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.rz_cols), _ptr(ws.wrz_cols), sw_all, _ptr(tmp), stream))
-                    torch.sum(tmp.view(-1, nel), 0, out=outg[out_row[peer]])      # the column slices, in index order
-            partner_work = dist.all_to_all_single(ing.view(-1), outg.view(-1), output_split_sizes=[x * plan.Dpad for x in out_split],
-                                                  input_split_sizes=[x * plan.Dpad for x in in_split], group=ws.group, async_op=True)
-        for first, n, st in ws.saved_blocks:        # blocks this rank evaluated in the forward: from their saved exponentials
-            entry_r, operand_r = ((lib.crossclr_backward_rect_saved_xfp, ws.xf_all) if remote_xfp else
-                                  (lib.crossclr_backward_rect_saved, ws.xcols))
-            nat.check(entry_r(pp, _ptr(operand_r), _ptr(st), first, n, ws.temperature, ws.negative_w,
-                              _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.rz_cols), _ptr(ws.wrz_cols), sw_all, _ptr(gbuf), 1, stream))
-        if ws.recompute_ranges:
-            ws.exchange.wait()                      # (point-to-point exchange: the slices only this recompute needs)
-        for first, n in ws.recompute_ranges:        # blocks the other side of a pair evaluated: recompute
-            nat.check(lib.crossclr_backward_ranks(pp, _ptr(ws.xhat), _ptr(ws.xcols), first, n, ws.temperature, ws.negative_w,
-                                                  _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.rz_cols), _ptr(ws.wrz_cols), sw_all,
-                                                  _ptr(gbuf), 1, stream))
-        if partner_work is not None:
-            _traced_wait("partner gradients", [partner_work])
-            g0 = gbuf[:nel]
-            for k in range(npairs):          # fixed order over the source ranks: deterministic
-                g0 += ing[k]
-        ws.saved_blocks = None
-        ws.xf = ws.xf_all = None
-    elif ws.sharded and ws.shift is None:
-        if ws.partner_peers is not None:
-            # Partner-gradient scheme (the default from 3 ranks): the first backward consumed the saved blocks, and the operand slices of
-            # the ranks whose blocks the PARTNER evaluated were never requested (deferred exchange) -- a recomputing launch over every
-            # rank's slice would read memory nobody wrote.  Every rank takes this branch together.
-            raise RuntimeError("CrossCLR (sharded, partner gradients): backward was called a second time through the same graph "
-                               "(retain_graph=True); the saved exponentials are released after the first backward and the late operand "
-                               "slices are never exchanged in this scheme -- run the forward again, or set CROSSCLR_PARTNER_GRADS=0 on "
-                               "every rank (the recomputing scheme supports repeated backwards)")
-        if ws.wrz_cols is None:
-            _traced_wait("statistics", [ws.stats_work])
-            ws.wrz_cols = ws.rz_cols * ws.negative_w
-        if ws.exchange is not None:
-            ws.exchange.wait()     # this launch reads EVERY rank's slice of xcols: also the late point-to-point ones
-        nat.check(lib.crossclr_backward_w(pp, _ptr(ws.xhat), _ptr(ws.xcols), world, 0, rank, ws.temperature,
-                                          ws.negative_w, _ptr(ws.rz), _ptr(ws.wrz), _ptr(ws.rz_cols),
-                                          _ptr(ws.wrz_cols), _sw(ws.k_rows, ws.k_cols, None), _ptr(gbuf), 1, stream))
-    if grad_out.dtype == torch.float64 and grad_out.device == dev and grad_out.numel() == 1:
-        go = grad_out.detach().reshape(1)
-    else:
-        go = grad_out.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
-    gv = torch.empty(video.shape, dtype=video.dtype, device=dev)
-    gt = torch.empty(text.shape, dtype=text.dtype, device=dev)
+        _backward_local(ws, gbuf, stream)
+        if ws.sharded and ws.saved_blocks is not None:
+            _backward_saved_remote(ws, gbuf, stream)
+        elif ws.sharded:
+            _backward_recompute_remote(ws, gbuf, stream)
+    go, gv, gt = _grad_buffers(video, text, grad_out)
     with _Range("crossclr.backward_finish"):
         nat.check(lib.crossclr_backward_finish_p(pp, _ptr(gbuf), _ptr(video), _ptr(text), video.stride(0), text.stride(0),
                                                  ws.in_dtype, _ptr(ws.inv_norm), ws.temperature, _sw(None, None, ws.lw),
@@ -1408,11 +1470,10 @@ class _CrossCLRFunction(torch.autograd.Function):
             # create_graph=True: the reference's eager ops (loss.py:79-114) are twice differentiable, so is this path (the same HIP
             # backward, recorded as a node whose own backward is the closed-form double backward on the device)
             gv, gt = _second_order_grads(ctx, video, text, grad_out)
-            return (gv if ctx.needs_input_grad[0] else None, gt if ctx.needs_input_grad[1] else None,
-                    None, None, None, None, None, None, None)
-        video_c, text_c = ctx.row_major
-        with _device_of(video_c):
-            gv, gt = _backward_impl(ctx.ws, video_c, text_c, grad_out)
+        else:
+            video_c, text_c = ctx.row_major
+            with _device_of(video_c):
+                gv, gt = _backward_impl(ctx.ws, video_c, text_c, grad_out)
         return (gv if ctx.needs_input_grad[0] else None, gt if ctx.needs_input_grad[1] else None,
                 None, None, None, None, None, None, None)
 
