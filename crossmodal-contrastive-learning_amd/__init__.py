@@ -13,6 +13,7 @@ from .influence import CrossCLR, influential_sample_weights
 from .ranking import MaxMargin_coot, cosine_sim, hardest_negatives, max_margin_loss, retrieval_ranks, retrieval_topk
 from .projection import ProjectedCrossCLR, projected_crossclr_loss
 from .infonce import InfoNCE, info_nce_loss
+from .sigmoid import SigmoidLoss, sigmoid_loss
 
 __all__ = ["CrossCLR_onlyIntraModality", "CrossCLR", "crossclr_loss", "all_gather_with_grad", "influential_sample_weights",
-           "MaxMargin_coot", "max_margin_loss", "cosine_sim", "retrieval_ranks", "retrieval_topk", "hardest_negatives", "InfoNCE", "info_nce_loss", "ProjectedCrossCLR", "projected_crossclr_loss", "AUTO_BF16_MIN_GLOBAL_BATCH", "_native"]
+           "MaxMargin_coot", "max_margin_loss", "cosine_sim", "retrieval_ranks", "retrieval_topk", "hardest_negatives", "InfoNCE", "info_nce_loss", "SigmoidLoss", "sigmoid_loss", "ProjectedCrossCLR", "projected_crossclr_loss", "AUTO_BF16_MIN_GLOBAL_BATCH", "_native"]

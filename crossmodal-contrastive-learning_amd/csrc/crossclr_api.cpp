@@ -8,6 +8,7 @@
 #include "crossclr_kernels_topk.h"
 #include "crossclr_kernels_hardneg.h"
 #include "crossclr_kernels_infonce.h"
+#include "crossclr_kernels_sigmoid.h"
 #include "crossclr_kernels_fast.h"
 #include "crossclr_kernels_project.h"
 #include "crossclr_kernels_saved32.h"
@@ -1768,6 +1769,106 @@ extern "C" int crossclr_infonce_backward_finish(const crossclr_plan* plan, const
         case CROSSCLR_IN_BF16: return CROSSCLR_IBF(in_bf16);
     }
 #undef CROSSCLR_IBF
+    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
+}
+
+// ------------------------------------------------------------------------------------------------
+// pairwise sigmoid loss with a logit scale and a logit bias in device memory (crossclr_kernels_sigmoid.h).  Plans and column splits are
+// those of the hardest-negative pass; there is no column side.
+// workspace, in floats: row softplus sums [ns][bpad] | row sigmoid sums [ns][bpad] | positive-pair scores [bpad]
+struct SigmoidWs { float* row_sp; float* row_sig; float* pair; };
+static size_t sigmoid_ws_words(const crossclr_plan* p, int ns) { return ((size_t)2 * ns + 1) * (size_t)p->bpad; }
+static SigmoidWs sigmoid_ws(const crossclr_plan* p, int ns, void* workspace) {
+    const size_t n = (size_t)p->bpad;
+    float* w = static_cast<float*>(workspace);
+    return {w, w + ns * n, w + 2 * ns * n};
+}
+extern "C" int crossclr_sigmoid_splits(const crossclr_plan* plan, int requested) {
+    if (int rc = hardneg_plan_ok("crossclr_sigmoid_splits", plan)) return rc;
+    return hardneg_splits(plan, requested);
+}
+extern "C" size_t crossclr_sigmoid_workspace_bytes(const crossclr_plan* plan, int splits) {
+    if (hardneg_plan_ok("crossclr_sigmoid_workspace_bytes", plan)) return 0;
+    return sigmoid_ws_words(plan, hardneg_splits(plan, splits)) * 4;
+}
+extern "C" int crossclr_sigmoid_stats(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias, int splits,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = hardneg_plan_ok("crossclr_sigmoid_stats", plan)) return rc;
+    if (!xhat || !logit_scale || !logit_bias || !workspace) return fail(CROSSCLR_E_ARG, "NULL argument");
+    const int ns = hardneg_splits(plan, splits);
+    const size_t need = sigmoid_ws_words(plan, ns) * 4;
+    if (workspace_bytes < need)
+        return fail(CROSSCLR_E_WORKSPACE, "crossclr_sigmoid_stats: workspace of %zu bytes, %zu needed (crossclr_sigmoid_workspace_bytes)", workspace_bytes, need);
+    const SigmoidWs ws = sigmoid_ws(plan, ns, workspace);
+    const int ntiles = plan->bpad / 128, tps = (ntiles + ns - 1) / ns;
+    return with_plan_type(plan, [&](auto t) {
+        using T = typename decltype(t)::type;
+        LAUNCH((sigmoid_stats_kernel<T>), dim3(ntiles, ns), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad, tps, logit_scale,
+               logit_bias, ws.row_sp, ws.row_sig, ws.pair);
+        return launch_status("sigmoid_stats_kernel");
+    });
+}
+extern "C" int crossclr_sigmoid_finish(const crossclr_plan* plan, const void* workspace, int splits, const float* logit_scale,
+                                       const float* logit_bias, float* row_loss, float* pair_score, double* loss_sum, double* sig_sum,
+                                       void* stream) {
+    if (int rc = hardneg_plan_ok("crossclr_sigmoid_finish", plan)) return rc;
+    if (!workspace || !logit_scale || !logit_bias || !row_loss || !pair_score || !loss_sum || !sig_sum) return fail(CROSSCLR_E_ARG, "NULL argument");
+    const int ns = hardneg_splits(plan, splits);
+    const SigmoidWs ws = sigmoid_ws(plan, ns, const_cast<void*>(workspace));
+    const int nb = plan->loss_ws_doubles - 1;
+    if (nb < 1) return fail(CROSSCLR_E_ARG, "bad plan");
+    LAUNCH(sigmoid_finish_kernel, dim3(nb), dim3(256), stream, (const float*)ws.row_sp, (const float*)ws.row_sig, ns, (const float*)ws.pair,
+           plan->bpad, plan->b, logit_scale, logit_bias, row_loss, pair_score, loss_sum, sig_sum);
+    // loss_sum[0] = sum_i row_loss[i], loss_sum[1] = that / B;  sig_sum[0] = sum_ij W[i][j], sig_sum[1] = that / B = dL/dbeta
+    LAUNCH(fwd_finish_reduce_kernel, dim3(1), dim3(64), stream, loss_sum, nb, 1.0 / (double)plan->b);
+    LAUNCH(fwd_finish_reduce_kernel, dim3(1), dim3(64), stream, sig_sum, nb, 1.0 / (double)plan->b);
+    return launch_status("sigmoid_finish_kernel");
+}
+extern "C" int crossclr_sigmoid_backward(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias,
+                                         float* gbuf, void* stream) {
+    if (int rc = hardneg_plan_ok("crossclr_sigmoid_backward", plan)) return rc;
+    if (!xhat || !logit_scale || !logit_bias || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
+    if (plan->bwd_slices < 1) return fail(CROSSCLR_E_ARG, "bad plan");
+    const int tps = (plan->bpad / 64 + plan->bwd_slices - 1) / plan->bwd_slices;
+    return with_plan_type(plan, [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_d_chunk<256, 128, 64>(plan->Dpad, [&](auto dc) {
+            constexpr int DC = decltype(dc)::value;
+            LAUNCH((sigmoid_backward_kernel<T, DC>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad,
+                   logit_scale, logit_bias, gbuf, tps);
+        });
+        return launch_status("sigmoid_backward_kernel");
+    });
+}
+template <typename TIN>
+static int sigmoid_backward_finish_t(const crossclr_plan* p, const float* gbuf, const void* video, const void* text, long ldv, long ldt,
+                                     const float* inv_norm, int normalized, const float* logit_scale, const double* grad_out, void* gvideo,
+                                     void* gtext, long ldgv, long ldgt, double* dscale, void* stream) {
+    const int nb = p->loss_ws_doubles - 1;
+    LAUNCH((sigmoid_backward_finish_kernel<TIN>), dim3(nb), dim3(256), stream, gbuf, p->bwd_slices, (const TIN*)video, (const TIN*)text, ldv, ldt,
+           p->b, p->bpad, p->D, p->Dpad, inv_norm, normalized, logit_scale, grad_out, (TIN*)gvideo, (TIN*)gtext, ldgv, ldgt, dscale);
+    // dscale[0] = grad_out * sum_p <x^_p, M_p> over the 2 B stacked rows (= 2 sum_ij W S), dscale[1] = that / (2 B) = grad_out * dL/ds
+    LAUNCH(fwd_finish_reduce_kernel, dim3(1), dim3(64), stream, dscale, nb, 0.5 / (double)p->b);
+    return launch_status("sigmoid_backward_finish_kernel");
+}
+extern "C" int crossclr_sigmoid_backward_finish(const crossclr_plan* plan, const float* gbuf, const void* video, const void* text, long ld_video,
+                                                long ld_text, int in_dtype, const float* inv_norm, int normalized, const float* logit_scale,
+                                                const double* grad_out, void* grad_video, void* grad_text, long ld_gvideo, long ld_gtext,
+                                                double* dscale, void* stream) {
+    if (int rc = hardneg_plan_ok("crossclr_sigmoid_backward_finish", plan)) return rc;
+    if (!gbuf || !video || !text || !logit_scale || !grad_out || !dscale || (normalized && !inv_norm)) return fail(CROSSCLR_E_ARG, "NULL argument");
+    if (plan->bwd_slices < 1 || plan->loss_ws_doubles < 2) return fail(CROSSCLR_E_ARG, "bad plan");
+    if (ld_video < plan->D || ld_text < plan->D || (grad_video && ld_gvideo < plan->D) || (grad_text && ld_gtext < plan->D))
+        return fail(CROSSCLR_E_ARG, "row stride smaller than D");
+#define CROSSCLR_SBF(TIN) sigmoid_backward_finish_t<TIN>(plan, gbuf, video, text, ld_video, ld_text, inv_norm, normalized, logit_scale, grad_out, \
+                                                         grad_video, grad_text, ld_gvideo, ld_gtext, dscale, stream)
+    switch (in_dtype) {
+        case CROSSCLR_IN_F32: return CROSSCLR_SBF(float);
+        case CROSSCLR_IN_F64: return CROSSCLR_SBF(double);
+        case CROSSCLR_IN_F16: return CROSSCLR_SBF(in_f16);
+        case CROSSCLR_IN_BF16: return CROSSCLR_SBF(in_bf16);
+    }
+#undef CROSSCLR_SBF
     return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
 }
 

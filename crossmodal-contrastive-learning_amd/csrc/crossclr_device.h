@@ -83,6 +83,9 @@ __device__ __forceinline__ s16x4 lds_read_tr16_b64(const void* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
 }
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+// v_log_f32 / v_rcp_f32 (1 ulp); no denormal handling: for arguments in the normal range (the sigmoid epilogues hand them 1 + t in [1, 2])
+__device__ __forceinline__ float fast_log2(float x) { return __builtin_amdgcn_logf(x); }
+__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float wave_xor_f32(float v, int mask) { return __shfl_xor(v, mask, 64); }
 __device__ __forceinline__ double wave_xor_f64(double v, int mask) { return __shfl_xor(v, mask, 64); }
 // value of lane (l ^ MASK) for MASK in {1, 2, 7, 15, 16}: DPP quad_perm / row_half_mirror / row_mirror
@@ -118,6 +121,10 @@ __device__ __forceinline__ double handoff_load_f64(const double* p) {
 }
 #endif
 
+#else
+// host forms for the emulated build (the rest of this layer's host forms come with hip_emu.h)
+inline float fast_log2(float x) { return log2f(x); }
+inline float fast_rcp(float x) { return 1.0f / x; }
 #endif
 
 // ---------------------------------------------------------------------------------------------

@@ -579,6 +579,51 @@ int crossclr_infonce_backward_finish(const crossclr_plan* plan, const float* gbu
                                      const double* grad_out, void* grad_video, void* grad_text, long ld_gvideo, long ld_gtext,
                                      double* dscale, void* stream);
 
+/* ---- pairwise sigmoid loss (SigLIP) with a logit scale and a logit bias in device memory (single device) ----------------------
+ *   z = s S + beta,  S = v^ . t^T:  every (video, text) pair is a binary problem of its own, positive on the diagonal,
+ *   L = 1/B [ sum_i softplus(-z[i][i]) + sum_{i != j} softplus(z[i][j]) ],  W[i][j] = sigma(z[i][j]) - [i == j],
+ *   dL/dv^ = s/B W t^,  dL/dt^ = s/B W^T v^,  dL/ds = 1/B sum_ij W[i][j] S[i][j],  dL/dbeta = 1/B sum_ij W[i][j].
+ * ABI: NEW SYMBOLS ONLY, CROSSCLR_ABI_VERSION stays 8 (the policy of crossclr_topk_*, crossclr_hardneg_* and crossclr_infonce_*).
+ *
+ * `plan` (world 1, any mode: CROSSCLR_MODE_BF16X3 included) and `xhat` are what crossclr_normalize (cosines) or crossclr_pack (rows as
+ * given) laid out.  `logit_scale` and `logit_bias` each point at ONE float in device memory, read by the kernels: the host never sees
+ * either value, so a captured graph replays with whatever the two scalars hold then.  Any finite values are valid, 0 and negative ones
+ * included.  Neither z, sigma(z) nor their gradients are materialised; W needs no row or column statistics, so the gradient product
+ * reads nothing the statistics pass wrote.  Padding is masked by index.  No atomics, every slot has one writer, sums run in a fixed
+ * order: the same inputs give the same bits.
+ * crossclr_sigmoid_stats  one pass over S in the log2 domain (x = c S + b2, c = s log2(e), b2 = beta log2(e)); fills `workspace`
+ *   (crossclr_sigmoid_workspace_bytes = (2 nsplit + 1) * bpad floats; contents irrelevant before) with each row's sums of
+ *   softplus(z) / ln 2 and of sigma(z) over the split's NEGATIVE pairs, and the positive pairs' S[i][i].  The positive pair stays out of
+ *   the fp32 sums: its softplus is about 10 at s = 10, beta = -10, next to negatives of 4.5e-5 each.
+ * crossclr_sigmoid_finish  adds a row's partials in split order and the positive pair's softplus(-z[i][i]) and -sigma(-z[i][i]), in
+ *   double.  row_loss[bpad] (float, nats; 0 for padding entries): row i's share of B L; pair_score[bpad] = S[i][i]; loss_sum and sig_sum
+ *   (plan->loss_ws_doubles doubles each): loss_sum[0] = sum_i row_loss[i], loss_sum[1] = that / B = L; sig_sum[0] = sum_ij W[i][j],
+ *   sig_sum[1] = that / B = dL/dbeta; from double partials added in a fixed order.
+ * crossclr_sigmoid_backward  the gradient product W . x^ of the stacked rows against the other modality, every score evaluated a second
+ *   time, the positive pair's -sigma(-z) inside its tile; fills gbuf (plan->gbuf_bytes, plan->bwd_slices slices: the layout of
+ *   crossclr_backward).  Its inputs are xhat, s and beta alone.
+ * crossclr_sigmoid_backward_finish  sums the slices and writes grad_out * dL/d(video, text) w.r.t. the caller's own row-major tensors in
+ *   their dtype: g = s/B M, followed by the normalize backward (g - x^ (x^ . g)) inv_norm when `normalized` (inv_norm as
+ *   crossclr_normalize wrote it; may be NULL otherwise).  grad_video or grad_text may be NULL (that gradient is not written).  dscale
+ *   (plan->loss_ws_doubles doubles): dscale[1] = grad_out * dL/ds, from the rows' <x^_p, M_p> -- no second pass over the scores.
+ *   grad_out: one device double.
+ * `splits`: 0 = the library's choice; > 0 = a request, cut down to what the shape allows.  Hand the SAME value to
+ *   crossclr_sigmoid_workspace_bytes, _stats and _finish; crossclr_sigmoid_splits returns the count they derive from it.
+ * The size query returns 0 and the others CROSSCLR_E_ARG for a bad plan or argument; CROSSCLR_E_WORKSPACE for a workspace that is too
+ * small.  Nothing is allocated, nothing synchronises, everything is enqueued on `stream`.                                          */
+int crossclr_sigmoid_splits(const crossclr_plan* plan, int splits);
+size_t crossclr_sigmoid_workspace_bytes(const crossclr_plan* plan, int splits);
+int crossclr_sigmoid_stats(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias, int splits,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int crossclr_sigmoid_finish(const crossclr_plan* plan, const void* workspace, int splits, const float* logit_scale,
+                            const float* logit_bias, float* row_loss, float* pair_score, double* loss_sum, double* sig_sum, void* stream);
+int crossclr_sigmoid_backward(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias, float* gbuf,
+                              void* stream);
+int crossclr_sigmoid_backward_finish(const crossclr_plan* plan, const float* gbuf, const void* video, const void* text, long ld_video,
+                                     long ld_text, int in_dtype, const float* inv_norm, int normalized, const float* logit_scale,
+                                     const double* grad_out, void* grad_video, void* grad_text, long ld_gvideo, long ld_gtext,
+                                     double* dscale, void* stream);
+
 /* ---- THE WHOLE STEP BEHIND TWO CALLS (ABI 6; layout handed from call to call and split workspace: ABI 7.  Single device: plan->world == 1)
  * What the reference's one class is to its caller (trainer/loss.py:68-114 `forward`, and autograd's backward through it): a binding needs
  * nothing but crossclr_make_plan, crossclr_step_plan, crossclr_step_forward and crossclr_step_backward.  The library chooses the kernels:
