@@ -199,6 +199,13 @@ _SIGNATURES = {
     "crossclr_sigmoid_backward": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _P, _P, _P, _P]),
     "crossclr_sigmoid_backward_finish": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _P, _P, ctypes.c_long, ctypes.c_long, ctypes.c_int, _P,
                                                         ctypes.c_int, _P, _P, _P, _P, ctypes.c_long, ctypes.c_long, _P, _P]),
+    # ABI version 8, additive symbols: pair ids of the two losses above (same-item pairs excluded); the _ids calls are the plain ones
+    # with the group array of crossclr_pair_groups as one more argument
+    "crossclr_pair_groups": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _P, _P]),
+    "crossclr_infonce_stats_ids": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _P, _P, ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "crossclr_infonce_backward_ids": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _P, _P, _P, _P, _P, _P]),
+    "crossclr_sigmoid_stats_ids": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "crossclr_sigmoid_backward_ids": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _P, _P, _P, _P, _P]),
     # ABI version 6: the whole single-device step behind two calls (the kernel-selection policy lives in the library);
     # ABI version 7: the layout crossclr_step_plan wrote is handed to both calls, the workspace is a persistent and a transient region
     "crossclr_step_plan": (ctypes.c_int, [ctypes.POINTER(Plan), ctypes.c_float, ctypes.c_float, ctypes.c_uint, ctypes.c_size_t,

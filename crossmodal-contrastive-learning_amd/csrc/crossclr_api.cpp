@@ -9,6 +9,7 @@
 #include "crossclr_kernels_hardneg.h"
 #include "crossclr_kernels_infonce.h"
 #include "crossclr_kernels_sigmoid.h"
+#include "crossclr_kernels_pairids.h"
 #include "crossclr_kernels_fast.h"
 #include "crossclr_kernels_project.h"
 #include "crossclr_kernels_saved32.h"
@@ -1675,6 +1676,17 @@ extern "C" int crossclr_hardneg_backward(const crossclr_plan* plan, const void* 
 }
 
 // ------------------------------------------------------------------------------------------------
+// pair_ids of the InfoNCE and the sigmoid loss (crossclr_kernels_pairids.h): int64 ids [b] -> int32 group [bpad] for the *_ids calls below
+extern "C" int crossclr_pair_groups(const crossclr_plan* plan, const int64_t* ids, int32_t* group_out, void* stream) {
+    if (int rc = hardneg_plan_ok("crossclr_pair_groups", plan)) return rc;
+    if (!ids || !group_out) return fail(CROSSCLR_E_ARG, "crossclr_pair_groups: NULL argument");
+    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "id and group types");
+    LAUNCH(pair_groups_kernel, dim3((plan->bpad + 255) / 256), dim3(256), stream, reinterpret_cast<const long long*>(ids), plan->b, plan->bpad,
+           reinterpret_cast<int*>(group_out));
+    return launch_status("pair_groups_kernel");
+}
+
+// ------------------------------------------------------------------------------------------------
 // symmetric InfoNCE with a logit scale in device memory (crossclr_kernels_infonce.h).  Plans, column splits and the workspace's size are
 // those of the hardest-negative pass: the same grid over the same tiles, (max, sum) pairs where that one keeps (score, index).
 // workspace, in floats: row maxima [ns][bpad] | row sums [ns][bpad] | column maxima [bpad / 128][bpad] | column sums, the same |
@@ -1693,22 +1705,37 @@ extern "C" size_t crossclr_infonce_workspace_bytes(const crossclr_plan* plan, in
     if (hardneg_plan_ok("crossclr_infonce_workspace_bytes", plan)) return 0;
     return hardneg_ws_words(plan, hardneg_splits(plan, splits)) * 4;
 }
-extern "C" int crossclr_infonce_stats(const crossclr_plan* plan, const void* xhat, const float* logit_scale, int splits, void* workspace,
-                                      size_t workspace_bytes, void* stream) {
-    if (int rc = hardneg_plan_ok("crossclr_infonce_stats", plan)) return rc;
+// `group` NULL: crossclr_infonce_stats; else crossclr_infonce_stats_ids (the same grid, workspace and split rule)
+static int infonce_stats(const char* what, const crossclr_plan* plan, const void* xhat, const float* logit_scale, const int32_t* group, int splits,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = hardneg_plan_ok(what, plan)) return rc;
     if (!xhat || !logit_scale || !workspace) return fail(CROSSCLR_E_ARG, "NULL argument");
     const int ns = hardneg_splits(plan, splits);
     const size_t need = hardneg_ws_words(plan, ns) * 4;
     if (workspace_bytes < need)
-        return fail(CROSSCLR_E_WORKSPACE, "crossclr_infonce_stats: workspace of %zu bytes, %zu needed (crossclr_infonce_workspace_bytes)", workspace_bytes, need);
+        return fail(CROSSCLR_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (crossclr_infonce_workspace_bytes)", what, workspace_bytes, need);
     const InfonceWs ws = infonce_ws(plan, ns, workspace);
     const int ntiles = plan->bpad / 128, tps = (ntiles + ns - 1) / ns;
     return with_plan_type(plan, [&](auto t) {
         using T = typename decltype(t)::type;
+        if (group) {
+            LAUNCH((infonce_stats_kernel<T, true, const int*>), dim3(ntiles, ns), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad, tps,
+                   logit_scale, ws.row_m, ws.row_s, ws.col_m, ws.col_s, ws.pair, (const int*)group);
+            return launch_status("infonce_stats_kernel<IDS>");
+        }
         LAUNCH((infonce_stats_kernel<T>), dim3(ntiles, ns), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad, tps, logit_scale,
                ws.row_m, ws.row_s, ws.col_m, ws.col_s, ws.pair);
         return launch_status("infonce_stats_kernel");
     });
+}
+extern "C" int crossclr_infonce_stats(const crossclr_plan* plan, const void* xhat, const float* logit_scale, int splits, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    return infonce_stats("crossclr_infonce_stats", plan, xhat, logit_scale, nullptr, splits, workspace, workspace_bytes, stream);
+}
+extern "C" int crossclr_infonce_stats_ids(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const int32_t* group, int splits,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+    if (!group) return fail(CROSSCLR_E_ARG, "crossclr_infonce_stats_ids: group is NULL (crossclr_pair_groups)");
+    return infonce_stats("crossclr_infonce_stats_ids", plan, xhat, logit_scale, group, splits, workspace, workspace_bytes, stream);
 }
 extern "C" int crossclr_infonce_finish(const crossclr_plan* plan, const void* workspace, int splits, const float* logit_scale, float* lse,
                                        float* pair_score, double* loss_sum, void* stream) {
@@ -1724,9 +1751,9 @@ extern "C" int crossclr_infonce_finish(const crossclr_plan* plan, const void* wo
     LAUNCH(fwd_finish_reduce_kernel, dim3(1), dim3(64), stream, loss_sum, nb, 0.5 / (double)plan->b);
     return launch_status("infonce_finish_kernel");
 }
-extern "C" int crossclr_infonce_backward(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* lse,
-                                         const float* pair_score, float* gbuf, void* stream) {
-    if (int rc = hardneg_plan_ok("crossclr_infonce_backward", plan)) return rc;
+static int infonce_backward(const char* what, const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* lse,
+                            const float* pair_score, const int32_t* group, float* gbuf, void* stream) {
+    if (int rc = hardneg_plan_ok(what, plan)) return rc;
     if (!xhat || !logit_scale || !lse || !pair_score || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
     if (plan->bwd_slices < 1) return fail(CROSSCLR_E_ARG, "bad plan");
     const int tps = (plan->bpad / 64 + plan->bwd_slices - 1) / plan->bwd_slices;
@@ -1734,11 +1761,24 @@ extern "C" int crossclr_infonce_backward(const crossclr_plan* plan, const void* 
         using T = typename decltype(t)::type;
         with_d_chunk<256, 128, 64>(plan->Dpad, [&](auto dc) {
             constexpr int DC = decltype(dc)::value;
-            LAUNCH((infonce_backward_kernel<T, DC>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad, logit_scale,
-                   lse, pair_score, gbuf, tps);
+            if (group)
+                LAUNCH((infonce_backward_kernel<T, DC, true, const int*>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad,
+                       logit_scale, lse, pair_score, gbuf, tps, (const int*)group);
+            else
+                LAUNCH((infonce_backward_kernel<T, DC>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad,
+                       logit_scale, lse, pair_score, gbuf, tps);
         });
-        return launch_status("infonce_backward_kernel");
+        return launch_status(group ? "infonce_backward_kernel<IDS>" : "infonce_backward_kernel");
     });
+}
+extern "C" int crossclr_infonce_backward(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* lse,
+                                         const float* pair_score, float* gbuf, void* stream) {
+    return infonce_backward("crossclr_infonce_backward", plan, xhat, logit_scale, lse, pair_score, nullptr, gbuf, stream);
+}
+extern "C" int crossclr_infonce_backward_ids(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* lse,
+                                             const float* pair_score, const int32_t* group, float* gbuf, void* stream) {
+    if (!group) return fail(CROSSCLR_E_ARG, "crossclr_infonce_backward_ids: group is NULL (crossclr_pair_groups)");
+    return infonce_backward("crossclr_infonce_backward_ids", plan, xhat, logit_scale, lse, pair_score, group, gbuf, stream);
 }
 template <typename TIN>
 static int infonce_backward_finish_t(const crossclr_plan* p, const float* gbuf, const void* video, const void* text, long ldv, long ldt,
@@ -1791,22 +1831,37 @@ extern "C" size_t crossclr_sigmoid_workspace_bytes(const crossclr_plan* plan, in
     if (hardneg_plan_ok("crossclr_sigmoid_workspace_bytes", plan)) return 0;
     return sigmoid_ws_words(plan, hardneg_splits(plan, splits)) * 4;
 }
-extern "C" int crossclr_sigmoid_stats(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias, int splits,
-                                      void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = hardneg_plan_ok("crossclr_sigmoid_stats", plan)) return rc;
+// `group` NULL: crossclr_sigmoid_stats; else crossclr_sigmoid_stats_ids (the same grid, workspace and split rule)
+static int sigmoid_stats(const char* what, const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias,
+                         const int32_t* group, int splits, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = hardneg_plan_ok(what, plan)) return rc;
     if (!xhat || !logit_scale || !logit_bias || !workspace) return fail(CROSSCLR_E_ARG, "NULL argument");
     const int ns = hardneg_splits(plan, splits);
     const size_t need = sigmoid_ws_words(plan, ns) * 4;
     if (workspace_bytes < need)
-        return fail(CROSSCLR_E_WORKSPACE, "crossclr_sigmoid_stats: workspace of %zu bytes, %zu needed (crossclr_sigmoid_workspace_bytes)", workspace_bytes, need);
+        return fail(CROSSCLR_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (crossclr_sigmoid_workspace_bytes)", what, workspace_bytes, need);
     const SigmoidWs ws = sigmoid_ws(plan, ns, workspace);
     const int ntiles = plan->bpad / 128, tps = (ntiles + ns - 1) / ns;
     return with_plan_type(plan, [&](auto t) {
         using T = typename decltype(t)::type;
+        if (group) {
+            LAUNCH((sigmoid_stats_kernel<T, true, const int*>), dim3(ntiles, ns), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad, tps,
+                   logit_scale, logit_bias, ws.row_sp, ws.row_sig, ws.pair, (const int*)group);
+            return launch_status("sigmoid_stats_kernel<IDS>");
+        }
         LAUNCH((sigmoid_stats_kernel<T>), dim3(ntiles, ns), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad, tps, logit_scale,
                logit_bias, ws.row_sp, ws.row_sig, ws.pair);
         return launch_status("sigmoid_stats_kernel");
     });
+}
+extern "C" int crossclr_sigmoid_stats(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias, int splits,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    return sigmoid_stats("crossclr_sigmoid_stats", plan, xhat, logit_scale, logit_bias, nullptr, splits, workspace, workspace_bytes, stream);
+}
+extern "C" int crossclr_sigmoid_stats_ids(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias,
+                                          const int32_t* group, int splits, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!group) return fail(CROSSCLR_E_ARG, "crossclr_sigmoid_stats_ids: group is NULL (crossclr_pair_groups)");
+    return sigmoid_stats("crossclr_sigmoid_stats_ids", plan, xhat, logit_scale, logit_bias, group, splits, workspace, workspace_bytes, stream);
 }
 extern "C" int crossclr_sigmoid_finish(const crossclr_plan* plan, const void* workspace, int splits, const float* logit_scale,
                                        const float* logit_bias, float* row_loss, float* pair_score, double* loss_sum, double* sig_sum,
@@ -1824,9 +1879,9 @@ extern "C" int crossclr_sigmoid_finish(const crossclr_plan* plan, const void* wo
     LAUNCH(fwd_finish_reduce_kernel, dim3(1), dim3(64), stream, sig_sum, nb, 1.0 / (double)plan->b);
     return launch_status("sigmoid_finish_kernel");
 }
-extern "C" int crossclr_sigmoid_backward(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias,
-                                         float* gbuf, void* stream) {
-    if (int rc = hardneg_plan_ok("crossclr_sigmoid_backward", plan)) return rc;
+static int sigmoid_backward(const char* what, const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias,
+                            const int32_t* group, float* gbuf, void* stream) {
+    if (int rc = hardneg_plan_ok(what, plan)) return rc;
     if (!xhat || !logit_scale || !logit_bias || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
     if (plan->bwd_slices < 1) return fail(CROSSCLR_E_ARG, "bad plan");
     const int tps = (plan->bpad / 64 + plan->bwd_slices - 1) / plan->bwd_slices;
@@ -1834,11 +1889,24 @@ extern "C" int crossclr_sigmoid_backward(const crossclr_plan* plan, const void* 
         using T = typename decltype(t)::type;
         with_d_chunk<256, 128, 64>(plan->Dpad, [&](auto dc) {
             constexpr int DC = decltype(dc)::value;
-            LAUNCH((sigmoid_backward_kernel<T, DC>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad,
-                   logit_scale, logit_bias, gbuf, tps);
+            if (group)
+                LAUNCH((sigmoid_backward_kernel<T, DC, true, const int*>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad,
+                       logit_scale, logit_bias, gbuf, tps, (const int*)group);
+            else
+                LAUNCH((sigmoid_backward_kernel<T, DC>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad,
+                       logit_scale, logit_bias, gbuf, tps);
         });
-        return launch_status("sigmoid_backward_kernel");
+        return launch_status(group ? "sigmoid_backward_kernel<IDS>" : "sigmoid_backward_kernel");
     });
+}
+extern "C" int crossclr_sigmoid_backward(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias,
+                                         float* gbuf, void* stream) {
+    return sigmoid_backward("crossclr_sigmoid_backward", plan, xhat, logit_scale, logit_bias, nullptr, gbuf, stream);
+}
+extern "C" int crossclr_sigmoid_backward_ids(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias,
+                                             const int32_t* group, float* gbuf, void* stream) {
+    if (!group) return fail(CROSSCLR_E_ARG, "crossclr_sigmoid_backward_ids: group is NULL (crossclr_pair_groups)");
+    return sigmoid_backward("crossclr_sigmoid_backward_ids", plan, xhat, logit_scale, logit_bias, group, gbuf, stream);
 }
 template <typename TIN>
 static int sigmoid_backward_finish_t(const crossclr_plan* p, const float* gbuf, const void* video, const void* text, long ldv, long ldt,

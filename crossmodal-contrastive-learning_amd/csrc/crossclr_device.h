@@ -25,6 +25,7 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef unsigned short bf16_t;  // storage type of a bf16 element in memory
 // storage type of one element of the split operand (compute_mode "bf16x3"): x = hi + lo, hi = bf16(x), lo = bf16(x - hi), both
 // round-to-nearest-even.  A row is laid out in 128-byte chunks of 32 elements, planar: the 32 hi values (64 B), then the 32 lo values.

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "crossclr_kernels_generic.h"
+#include "crossclr_kernels_pairids.h"
 
 namespace crossclr {
 
@@ -95,14 +96,26 @@ __device__ __forceinline__ void halving_lse16(const float (&m)[16], const float 
 //   pair[i] = S[i][i] from the diagonal tile's accumulators.
 //   LDS: 2 x 16 KiB operand chunks + 4 KiB of reduction slots.
 // ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(256, 2) infonce_stats_kernel(const T* X, int b, int bpad, int Dpad, int tiles_per_split,
-                                                               const float* logit_scale, float* row_m, float* row_s, float* col_m,
-                                                               float* col_s, float* pair) {
+//   IDS (pair ids, crossclr_kernels_pairids.h): group [bpad]; an entry (i, j), i != j, with group[i] == group[j] is left out of row i's and
+//   of column j's soft-max -- kInfonceMasked in both maxima, no term of either sum, exactly like padding; every tile takes the masked
+//   epilogue.  A slot whose entries are all left out is the empty slot.  ONE wave per SIMD for these instantiations: the masks do not fit
+//   beside the 254 registers of the plain ones.
+template <typename T, bool IDS = false, typename... GROUP>
+__global__ void __launch_bounds__(256, IDS ? 1 : 2) infonce_stats_kernel(const T* X, int b, int bpad, int Dpad, int tiles_per_split,
+                                                                         const float* logit_scale, float* row_m, float* row_s, float* col_m,
+                                                                         float* col_s, float* pair, GROUP... group_arg) {
     typedef Operand<T> Op;
+    static_assert(sizeof...(GROUP) == (IDS ? 1 : 0), "IDS instantiations take the group array as their last argument");
+    const int* group = group_of(group_arg...);
     CROSSCLR_SHARED __attribute__((aligned(16))) unsigned char lds[2 * 128 * 128];
     CROSSCLR_SHARED float red_m[4 * 128];
     CROSSCLR_SHARED float red_s[4 * 128];
+    int* colg = nullptr;      // IDS: the groups of the tile's 128 columns, two tiles' worth (a tile's readers and the next one's writers
+    int rg[2] = {0, 0};       // never meet in one half), and of the lane's two rows
+    if constexpr (IDS) {
+        CROSSCLR_SHARED __attribute__((aligned(16))) int col_groups[2 * 128];
+        colg = col_groups;
+    }
     unsigned char* tileP = lds;                 // video chunk [128][128 B]
     unsigned char* tileQ = lds + 128 * 128;     // text chunk  [128][128 B]
     float* const redm = red_m;
@@ -124,10 +137,17 @@ __global__ void __launch_bounds__(256, 2) infonce_stats_kernel(const T* X, int b
 
     float run_m[2] = {kInfonceMasked, kInfonceMasked};
     float run_u[2] = {-1.f, -1.f};
+    if constexpr (IDS) {
+        rg[0] = group[row0 + 64 * wr + l31];
+        rg[1] = group[row0 + 64 * wr + 32 + l31];
+    }
 
     KTileStage<128, 256> sp, sq, sp2, sq2;
     for (int t = t_begin; t < t_end; ++t) {
         const unsigned char* cbase = tbase + (size_t)t * 128 * pitch;
+        if constexpr (IDS) {      // read in the epilogue, behind the main loop's barriers
+            if (tid < 128) colg[(t & 1) * 128 + tid] = group[t * 128 + tid];
+        }
         f32x16 acc[2][2];
 #pragma unroll
         for (int a = 0; a < 2; ++a)
@@ -186,6 +206,15 @@ __global__ void __launch_bounds__(256, 2) infonce_stats_kernel(const T* X, int b
         auto epilogue = [&](auto masked_c) {
             constexpr bool MASKED = decltype(masked_c)::value;
             const bool row_ok[2] = {row0 + 64 * wr + l31 < b, row0 + 64 * wr + 32 + l31 < b};
+            // IDS: an entry of another pair of the row's own item is no entry at all -- out of both maxima and both sums, like padding
+            auto same_item = [&](int pi, int qi, int r) {
+                if constexpr (IDS) {
+                    const int cl = 64 * wc + 32 * qi + frag_row(r, half);
+                    return colg[(t & 1) * 128 + cl] == rg[pi] && t * 128 + cl != row0 + 64 * wr + 32 * pi + l31;
+                } else {
+                    return false;
+                }
+            };
             // row side, step 1: the tile's maximum of each of the lane's two rows, one rescale of the running sum
             float tm[2] = {kInfonceMasked, kInfonceMasked};
 #pragma unroll
@@ -196,7 +225,9 @@ __global__ void __launch_bounds__(256, 2) infonce_stats_kernel(const T* X, int b
 #pragma unroll
                     for (int pi = 0; pi < 2; ++pi) {
                         const float x = infonce_logit(c, acc[qi][pi][r]);
-                        tm[pi] = fmaxf(tm[pi], (!MASKED || (col_ok && row_ok[pi])) ? x : kInfonceMasked);
+                        bool ok = !MASKED || (col_ok && row_ok[pi]);
+                        if constexpr (IDS) ok = ok && !same_item(pi, qi, r);
+                        tm[pi] = fmaxf(tm[pi], ok ? x : kInfonceMasked);
                     }
                 }
             float ts[2] = {0.f, 0.f}, ties[2] = {0.f, 0.f};      // the tile's terms below the maximum, and how many attain it
@@ -217,7 +248,11 @@ __global__ void __launch_bounds__(256, 2) infonce_stats_kernel(const T* X, int b
                 for (int r = 0; r < 16; ++r) {
                     const bool col_ok = !MASKED || col0 + 32 * qi + frag_row(r, half) < b;
                     const float x0 = infonce_logit(c, acc[qi][0][r]), x1 = infonce_logit(c, acc[qi][1][r]);
-                    const bool ok0 = !MASKED || (col_ok && row_ok[0]), ok1 = !MASKED || (col_ok && row_ok[1]);
+                    bool ok0 = !MASKED || (col_ok && row_ok[0]), ok1 = !MASKED || (col_ok && row_ok[1]);
+                    if constexpr (IDS) {
+                        ok0 = ok0 && !same_item(0, qi, r);
+                        ok1 = ok1 && !same_item(1, qi, r);
+                    }
                     const bool top0 = x0 == run_m[0], top1 = x1 == run_m[1];
                     ts[0] += (ok0 && !top0) ? fast_exp2(x0 - run_m[0]) : 0.f;
                     ts[1] += (ok1 && !top1) ? fast_exp2(x1 - run_m[1]) : 0.f;
@@ -243,7 +278,7 @@ __global__ void __launch_bounds__(256, 2) infonce_stats_kernel(const T* X, int b
 #pragma unroll
             for (int pi = 0; pi < 2; ++pi) run_u[pi] += ts[pi] + ties[pi];
         };
-        if (ragged_rows || t * 128 + 128 > b) epilogue(std::true_type());      // (block-uniform)
+        if (IDS || ragged_rows || t * 128 + 128 > b) epilogue(std::true_type());      // (block-uniform)
         else epilogue(std::false_type());
         __syncthreads();
         if (tid < 128) {
@@ -339,10 +374,14 @@ __global__ void __launch_bounds__(256) infonce_finish_kernel(const float* row_m,
 // grid = (2 bpad / 64, Dpad / DC, slices); slice z walks tiles [z tps, (z + 1) tps) of the other modality's bpad / 64 and writes its own
 // gbuf slice [2 bpad][Dpad] (a slice without tiles writes zeros).  Every score is evaluated here a second time.
 // ---------------------------------------------------------------------------------------------
-template <typename T, int DC>
+// IDS (pair ids): group [bpad], the same array for the video rows and the text rows: W is SELECTED to 0 where the statistics left the
+// entry out (its logit was in neither log-sum-exp and may lie far above both: exp2 gives inf), before the operand split sees it.
+template <typename T, int DC, bool IDS = false, typename... GROUP>
 __global__ void __launch_bounds__(256) infonce_backward_kernel(const T* X, int b, int bpad, int Dpad, const float* logit_scale, const float* lse,
-                                                               const float* pair, float* gbuf, int tiles_per_slice) {
+                                                               const float* pair, float* gbuf, int tiles_per_slice, GROUP... group_arg) {
     typedef Operand<T> Op;
+    static_assert(sizeof...(GROUP) == (IDS ? 1 : 0), "IDS instantiations take the group array as their last argument");
+    const int* group = group_of(group_arg...);
     typedef BwdLds<T, DC> L;
     CROSSCLR_SHARED __attribute__((aligned(16))) unsigned char lds[L::kTotal];
     unsigned char* tileP = lds + L::kTileP;
@@ -375,6 +414,8 @@ __global__ void __launch_bounds__(256) infonce_backward_kernel(const T* X, int b
     const float lse_p = lse[row0 + p_t], lse_p_lo = lse[2 * bpad + row0 + p_t];
     const bool p_ok = r_in_mod0 + p_t < b;
     const float x_pp = infonce_logit(c, pair[r_in_mod0 + p_t]);      // the positive pair's logit as the statistics saw it
+    int grp_p = 0;
+    if constexpr (IDS) grp_p = group[r_in_mod0 + p_t];
 
     const int ntiles = bpad / 64;
     const int t_begin = blockIdx.z * tiles_per_slice;
@@ -424,6 +465,8 @@ __global__ void __launch_bounds__(256) infonce_backward_kernel(const T* X, int b
             const int q0 = 32 * wq + 8 * r4 + 4 * half;  // frag_row(4 r4 + j, half) = q0 - 32 wq + j
             const f32x4 lq = *reinterpret_cast<const f32x4*>(lse_cols + in_mod0 + q0);
             const f32x4 lq_lo = *reinterpret_cast<const f32x4*>(lse_cols + 2 * bpad + in_mod0 + q0);
+            i32x4 gq = {0, 0, 0, 0};
+            if constexpr (IDS) gq = *reinterpret_cast<const i32x4*>(group + in_mod0 + q0);
             f32x4 w;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -433,6 +476,9 @@ __global__ void __launch_bounds__(256) infonce_backward_kernel(const T* X, int b
                 if (diag_tile && q0 + j == p_t)      // (P - 1) + (P' - 1) without forming a P near 1
                     v = expm1f(((x_pp - lse_p) - lse_p_lo) * kLn2) + expm1f(((x_pp - lq[j]) - lq_lo[j]) * kLn2);
                 if (!p_ok || (ragged && in_mod0 + q0 + j >= b)) v = 0.f;
+                // IDS: another pair of the row's own item.  Its logit was in neither log-sum-exp and may lie far above both (v = inf):
+                // the weight is SELECTED to 0 before the operand split sees it
+                if constexpr (IDS) v = (gq[j] == grp_p && in_mod0 + q0 + j != r_in_mod0 + p_t) ? 0.f : v;
                 w[j] = v;
             }
             w_store4(wt, p_t, q0, w, (T*)nullptr);

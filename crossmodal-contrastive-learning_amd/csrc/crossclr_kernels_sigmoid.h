@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "crossclr_kernels_generic.h"
+#include "crossclr_kernels_pairids.h"
 
 namespace crossclr {
 
@@ -50,14 +51,24 @@ __device__ __forceinline__ float sigmoid_pair_weight(float x, const SigmoidTerms
 //   tile's accumulators.
 //   LDS: 2 x 16 KiB operand chunks + 4 KiB of reduction slots.
 // ---------------------------------------------------------------------------------------------
-template <typename T>
+//   IDS (pair ids, crossclr_kernels_pairids.h): group [bpad]; an entry (i, j), i != j, with group[i] == group[j] is no negative pair and
+//   stays out of both row sums; every tile takes the masked epilogue.
+template <typename T, bool IDS = false, typename... GROUP>
 __global__ void __launch_bounds__(256, 2) sigmoid_stats_kernel(const T* X, int b, int bpad, int Dpad, int tiles_per_split,
                                                                const float* logit_scale, const float* logit_bias, float* row_sp,
-                                                               float* row_sig, float* pair) {
+                                                               float* row_sig, float* pair, GROUP... group_arg) {
     typedef Operand<T> Op;
+    static_assert(sizeof...(GROUP) == (IDS ? 1 : 0), "IDS instantiations take the group array as their last argument");
+    const int* group = group_of(group_arg...);
     CROSSCLR_SHARED __attribute__((aligned(16))) unsigned char lds[2 * 128 * 128];
     CROSSCLR_SHARED float red_sp[4 * 128];
     CROSSCLR_SHARED float red_sg[4 * 128];
+    int* colg = nullptr;      // IDS: the groups of the tile's 128 columns, two tiles' worth (a tile's readers and the next one's writers
+    int rg[2] = {0, 0};       // never meet in one half), and of the lane's two rows
+    if constexpr (IDS) {
+        CROSSCLR_SHARED __attribute__((aligned(16))) int col_groups[2 * 128];
+        colg = col_groups;
+    }
     unsigned char* tileP = lds;                 // video chunk [128][128 B]
     unsigned char* tileQ = lds + 128 * 128;     // text chunk  [128][128 B]
 
@@ -76,10 +87,17 @@ __global__ void __launch_bounds__(256, 2) sigmoid_stats_kernel(const T* X, int b
     const float c = logit_scale[0] * kLog2e, b2 = logit_bias[0] * kLog2e;
 
     float run_sp[2] = {0.f, 0.f}, run_sg[2] = {0.f, 0.f};
+    if constexpr (IDS) {
+        rg[0] = group[row0 + 64 * wr + l31];
+        rg[1] = group[row0 + 64 * wr + 32 + l31];
+    }
 
     KTileStage<128, 256> sp, sq, sp2, sq2;
     for (int t = t_begin; t < t_end; ++t) {
         const unsigned char* cbase = tbase + (size_t)t * 128 * pitch;
+        if constexpr (IDS) {      // read in the epilogue, behind the main loop's barriers
+            if (tid < 128) colg[(t & 1) * 128 + tid] = group[t * 128 + tid];
+        }
         f32x16 acc[2][2];
 #pragma unroll
         for (int a = 0; a < 2; ++a)
@@ -142,11 +160,14 @@ __global__ void __launch_bounds__(256, 2) sigmoid_stats_kernel(const T* X, int b
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int col = col0 + 32 * qi + frag_row(r, half);
+                    int cg = 0;
+                    if constexpr (IDS) cg = colg[(t & 1) * 128 + col - t * 128];
 #pragma unroll
                     for (int pi = 0; pi < 2; ++pi) {
                         const float x = fmaf(c, acc[qi][pi][r], b2);
                         const SigmoidTerms e = sigmoid_terms(x);
-                        const bool ok = !MASKED || (col < b && row[pi] < b && col != row[pi]);
+                        // IDS: the pairs of the row's own item are no negatives (the positive pair, of the same group, is the finish's)
+                        const bool ok = !MASKED || (col < b && row[pi] < b && (IDS ? cg != rg[pi] : col != row[pi]));
                         ts[pi] += ok ? sigmoid_softplus2(x, e) : 0.f;
                         tg[pi] += ok ? sigmoid_sigma(x, e) : 0.f;
                     }
@@ -157,7 +178,7 @@ __global__ void __launch_bounds__(256, 2) sigmoid_stats_kernel(const T* X, int b
                 run_sg[pi] += tg[pi];
             }
         };
-        if (ragged_rows || t * 128 + 128 > b || t == rb) epilogue(std::true_type());      // (block-uniform)
+        if (IDS || ragged_rows || t * 128 + 128 > b || t == rb) epilogue(std::true_type());      // (block-uniform)
         else epilogue(std::false_type());
     }
     // the four lanes (wc, half) that share a row, in a fixed order
@@ -237,10 +258,14 @@ __global__ void __launch_bounds__(256) sigmoid_finish_kernel(const float* row_sp
 // grid = (2 bpad / 64, Dpad / DC, slices); slice z walks tiles [z tps, (z + 1) tps) of the other modality's bpad / 64 and writes its own
 // gbuf slice [2 bpad][Dpad] (a slice without tiles writes zeros).  Inputs: the packed operand, s and beta -- no saved statistics.
 // ---------------------------------------------------------------------------------------------
-template <typename T, int DC>
+// IDS (pair ids): group [bpad], the same array for the video rows and the text rows: W = 0 where the statistics left the entry out.
+template <typename T, int DC, bool IDS = false, typename... GROUP>
 __global__ void __launch_bounds__(256) sigmoid_backward_kernel(const T* X, int b, int bpad, int Dpad, const float* logit_scale,
-                                                               const float* logit_bias, float* gbuf, int tiles_per_slice) {
+                                                               const float* logit_bias, float* gbuf, int tiles_per_slice,
+                                                               GROUP... group_arg) {
     typedef Operand<T> Op;
+    static_assert(sizeof...(GROUP) == (IDS ? 1 : 0), "IDS instantiations take the group array as their last argument");
+    const int* group = group_of(group_arg...);
     typedef BwdLds<T, DC> L;
     CROSSCLR_SHARED __attribute__((aligned(16))) unsigned char lds[L::kTotal];
     unsigned char* tileP = lds + L::kTileP;
@@ -270,6 +295,8 @@ __global__ void __launch_bounds__(256) sigmoid_backward_kernel(const T* X, int b
 
     const int p_t = 32 * wp + l31;      // this lane's row inside the block (phase B)
     const bool p_ok = r_in_mod0 + p_t < b;
+    int grp_p = 0;
+    if constexpr (IDS) grp_p = group[r_in_mod0 + p_t];
 
     const int ntiles = bpad / 64;
     const int t_begin = blockIdx.z * tiles_per_slice;
@@ -317,6 +344,8 @@ __global__ void __launch_bounds__(256) sigmoid_backward_kernel(const T* X, int b
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4) {
             const int q0 = 32 * wq + 8 * r4 + 4 * half;  // frag_row(4 r4 + j, half) = q0 - 32 wq + j
+            i32x4 gq = {0, 0, 0, 0};
+            if constexpr (IDS) gq = *reinterpret_cast<const i32x4*>(group + in_mod0 + q0);
             f32x4 w;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -325,6 +354,7 @@ __global__ void __launch_bounds__(256) sigmoid_backward_kernel(const T* X, int b
                 float v = sigmoid_sigma(x, e);
                 if (diag_tile && q0 + j == p_t) v = sigmoid_pair_weight(x, e);
                 if (!p_ok || (ragged && in_mod0 + q0 + j >= b)) v = 0.f;
+                if constexpr (IDS) v = (gq[j] == grp_p && in_mod0 + q0 + j != r_in_mod0 + p_t) ? 0.f : v;      // another pair of the row's own item
                 w[j] = v;
             }
             w_store4(wt, p_t, q0, w, (T*)nullptr);

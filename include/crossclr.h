@@ -30,6 +30,7 @@
 #define CROSSCLR_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -623,6 +624,35 @@ int crossclr_sigmoid_backward_finish(const crossclr_plan* plan, const float* gbu
                                      long ld_text, int in_dtype, const float* inv_norm, int normalized, const float* logit_scale,
                                      const double* grad_out, void* grad_video, void* grad_text, long ld_gvideo, long ld_gtext,
                                      double* dscale, void* stream);
+
+/* ---- pair ids for the two losses above: same-item pairs are EXCLUDED, never positives (single device) --------------------------
+ *   ids[i] names the item that pair i (video i and text i) belongs to.  An entry (i, j) with i != j and ids[i] == ids[j] (all 64 bits;
+ *   negative values are ids like any other) is a false negative and is taken OUT of the loss; the positive pair (i, i) never is.
+ *   InfoNCE: the entry leaves row i's AND column j's soft-max, maximum and sum alike; the divisor stays 2 B; W = 0 there, and
+ *     dL/ds = 1/(2B) sum_ij W[i][j] S[i][j] holds as it stands.  Sigmoid: its softplus(z) leaves row_loss[i] and the loss (divisor B),
+ *     W = 0 there, dL/dbeta = 1/B sum_ij W[i][j] without it.  Same-item pairs are NOT additional positive targets (no SupCon / UniCL).
+ * ABI: NEW SYMBOLS ONLY, CROSSCLR_ABI_VERSION stays 8.  The B x B mask is never formed: the tiled epilogues evaluate it per entry.
+ *
+ * crossclr_pair_groups  ids[b] (int64, device) -> group_out[plan->bpad] (int32, device): group[i] = the smallest j with ids[j] == ids[i],
+ *   group[i] = i for the padding rows; two pairs share an item exactly when their groups are equal, and the groups depend on the
+ *   partition the ids induce, not on their labels.  O(B^2) integer compares, staged through LDS; enqueue it once per step, ahead of:
+ * crossclr_infonce_stats_ids / crossclr_infonce_backward_ids / crossclr_sigmoid_stats_ids / crossclr_sigmoid_backward_ids  the calls
+ *   without _ids with `group` (what crossclr_pair_groups wrote for THIS plan) as one more argument: every other argument, the workspace
+ *   size, the split rule, the outputs' layout and the finish calls that follow (crossclr_infonce_finish, crossclr_sigmoid_finish and the
+ *   two _backward_finish) are those of the plain calls.  A row or column whose split holds excluded entries only contributes the empty
+ *   partial.  Hand the backward the group array the statistics saw.
+ * The ids' VALUES never reach the host: a captured graph replays with whatever the ids tensor holds then.  No atomics, one writer per
+ * slot, fixed merge order.  CROSSCLR_E_ARG for a NULL ids / group pointer or a plan the plain calls refuse; nothing is allocated,
+ * nothing synchronises, everything is enqueued on `stream`.                                                                         */
+int crossclr_pair_groups(const crossclr_plan* plan, const int64_t* ids, int32_t* group_out, void* stream);
+int crossclr_infonce_stats_ids(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const int32_t* group, int splits,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int crossclr_infonce_backward_ids(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* lse,
+                                  const float* pair_score, const int32_t* group, float* gbuf, void* stream);
+int crossclr_sigmoid_stats_ids(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias,
+                               const int32_t* group, int splits, void* workspace, size_t workspace_bytes, void* stream);
+int crossclr_sigmoid_backward_ids(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias,
+                                  const int32_t* group, float* gbuf, void* stream);
 
 /* ---- THE WHOLE STEP BEHIND TWO CALLS (ABI 6; layout handed from call to call and split workspace: ABI 7.  Single device: plan->world == 1)
  * What the reference's one class is to its caller (trainer/loss.py:68-114 `forward`, and autograd's backward through it): a binding needs
