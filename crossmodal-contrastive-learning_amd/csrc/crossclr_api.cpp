@@ -92,6 +92,16 @@ template <bool SPLIT = true, class F> static int with_plan_type(const crossclr_p
     if constexpr (SPLIT) if (is_x3(plan)) return f(type_tag<x3_t>());
     return f(type_tag<bf16_t>());
 }
+// the caller's element type from in_dtype -- f(type_tag<float>()), <double>, <in_f16> or <in_bf16>
+template <class F> static int with_in_dtype(int in_dtype, F f) {
+    switch (in_dtype) {
+        case CROSSCLR_IN_F32: return f(type_tag<float>());
+        case CROSSCLR_IN_F64: return f(type_tag<double>());
+        case CROSSCLR_IN_F16: return f(type_tag<in_f16>());
+        case CROSSCLR_IN_BF16: return f(type_tag<in_bf16>());
+    }
+    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
+}
 // D columns per thread block: the first of DCS... that divides Dpad (the last one, 64, always does) -- f(std::integral_constant<int, DC>())
 template <int DC, int... REST, class F> static void with_d_chunk(int Dpad, F f) {
     if constexpr (sizeof...(REST) == 0) f(std::integral_constant<int, DC>());
@@ -346,13 +356,9 @@ static int normalize_any(const crossclr_plan* plan, const void* video, const voi
                          void* xhat, float* inv_norm, float* diag_cos, void* stream, int* zero_word = nullptr) {
     if (!plan || !video || !text || !xhat || !inv_norm || !diag_cos) return fail(CROSSCLR_E_ARG, "NULL argument");
     if (ld_video < plan->D || ld_text < plan->D) return fail(CROSSCLR_E_ARG, "row stride smaller than D");
-    switch (in_dtype) {
-        case CROSSCLR_IN_F32: return normalize_t<float, NORM>(plan, video, text, ld_video, ld_text, xhat, inv_norm, diag_cos, stream, zero_word);
-        case CROSSCLR_IN_F64: return normalize_t<double, NORM>(plan, video, text, ld_video, ld_text, xhat, inv_norm, diag_cos, stream, zero_word);
-        case CROSSCLR_IN_F16: return normalize_t<in_f16, NORM>(plan, video, text, ld_video, ld_text, xhat, inv_norm, diag_cos, stream, zero_word);
-        case CROSSCLR_IN_BF16: return normalize_t<in_bf16, NORM>(plan, video, text, ld_video, ld_text, xhat, inv_norm, diag_cos, stream, zero_word);
-    }
-    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
+    return with_in_dtype(in_dtype, [&](auto tin) {
+        return normalize_t<typename decltype(tin)::type, NORM>(plan, video, text, ld_video, ld_text, xhat, inv_norm, diag_cos, stream, zero_word);
+    });
 }
 
 template <typename TIN, bool NORM>
@@ -378,13 +384,9 @@ static int normalize_xf_any(const crossclr_plan* plan, const void* video, const 
         if (int rc = normalize_any<NORM>(plan, video, text, ld_video, ld_text, in_dtype, xhat, inv_norm, diag_cos, stream, zero_word)) return rc;
         return crossclr_pack_xf_from_packed(plan, xhat, 1, xf, stream);
     }
-    switch (in_dtype) {
-        case CROSSCLR_IN_F32: return normalize_xf_t<float, NORM>(plan, video, text, ld_video, ld_text, xhat, xf, inv_norm, diag_cos, stream, zero_word);
-        case CROSSCLR_IN_F64: return normalize_xf_t<double, NORM>(plan, video, text, ld_video, ld_text, xhat, xf, inv_norm, diag_cos, stream, zero_word);
-        case CROSSCLR_IN_F16: return normalize_xf_t<in_f16, NORM>(plan, video, text, ld_video, ld_text, xhat, xf, inv_norm, diag_cos, stream, zero_word);
-        case CROSSCLR_IN_BF16: return normalize_xf_t<in_bf16, NORM>(plan, video, text, ld_video, ld_text, xhat, xf, inv_norm, diag_cos, stream, zero_word);
-    }
-    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
+    return with_in_dtype(in_dtype, [&](auto tin) {
+        return normalize_xf_t<typename decltype(tin)::type, NORM>(plan, video, text, ld_video, ld_text, xhat, xf, inv_norm, diag_cos, stream, zero_word);
+    });
 }
 extern "C" int crossclr_normalize_xf(const crossclr_plan* plan, const void* video, const void* text, long ld_video, long ld_text,
                                      int in_dtype, void* xhat, void* xhat_xf, float* inv_norm, float* diag_cos, void* stream) {
@@ -444,13 +446,10 @@ static int project_pack_any(const crossclr_plan* plan, const void* x_video, cons
     if (Din_video < 1 || Din_text < 1 || ld_video < Din_video || ld_text < Din_text) return fail(CROSSCLR_E_ARG, "row stride smaller than Din");
     if (ldw_video % 64 != 0 || ldw_video < Din_video || ldw_text % 64 != 0 || ldw_text < Din_text)
         return fail(CROSSCLR_E_ARG, "weights must be zero-padded to ldw = a multiple of 64 >= Din (got %d / %d for Din %d / %d)", ldw_video, ldw_text, Din_video, Din_text);
-    switch (in_dtype) {
-        case CROSSCLR_IN_F32: return project_pack_t<float, WF>(plan, x_video, x_text, ld_video, ld_text, Din_video, Din_text, w_video, w_text, ldw_video, ldw_text, bias_video, bias_text, xhat, inv_norm, diag_cos, stream);
-        case CROSSCLR_IN_F64: return project_pack_t<double, WF>(plan, x_video, x_text, ld_video, ld_text, Din_video, Din_text, w_video, w_text, ldw_video, ldw_text, bias_video, bias_text, xhat, inv_norm, diag_cos, stream);
-        case CROSSCLR_IN_F16: return project_pack_t<in_f16, WF>(plan, x_video, x_text, ld_video, ld_text, Din_video, Din_text, w_video, w_text, ldw_video, ldw_text, bias_video, bias_text, xhat, inv_norm, diag_cos, stream);
-        case CROSSCLR_IN_BF16: return project_pack_t<in_bf16, WF>(plan, x_video, x_text, ld_video, ld_text, Din_video, Din_text, w_video, w_text, ldw_video, ldw_text, bias_video, bias_text, xhat, inv_norm, diag_cos, stream);
-    }
-    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
+    return with_in_dtype(in_dtype, [&](auto tin) {
+        return project_pack_t<typename decltype(tin)::type, WF>(plan, x_video, x_text, ld_video, ld_text, Din_video, Din_text, w_video, w_text, ldw_video,
+                                                                ldw_text, bias_video, bias_text, xhat, inv_norm, diag_cos, stream);
+    });
 }
 extern "C" int crossclr_project_pack(const crossclr_plan* plan, const void* x_video, const void* x_text, long ld_video, long ld_text,
                                      int Din_video, int Din_text, int in_dtype, const void* w_video, const void* w_text, int ldw_video,
@@ -502,13 +501,10 @@ extern "C" int crossclr_project_dw(int b, int D, const void* gy_video, const voi
     if (!gy_video || !gy_text || !x_video || !x_text || !ws || !dw_video || !dw_text) return fail(CROSSCLR_E_ARG, "NULL argument");
     if (b < 1 || D < 1 || Din_video < 1 || Din_text < 1 || ld_gy < D || ld_xv < Din_video || ld_xt < Din_text || ld_dwv < Din_video || ld_dwt < Din_text)
         return fail(CROSSCLR_E_ARG, "crossclr_project_dw: bad sizes / strides");
-    switch (in_dtype) {
-        case CROSSCLR_IN_F32: return project_dw_t<float>(b, D, gy_video, gy_text, ld_gy, x_video, x_text, ld_xv, ld_xt, Din_video, Din_text, ws, dw_video, dw_text, ld_dwv, ld_dwt, db_video, db_text, stream);
-        case CROSSCLR_IN_F64: return project_dw_t<double>(b, D, gy_video, gy_text, ld_gy, x_video, x_text, ld_xv, ld_xt, Din_video, Din_text, ws, dw_video, dw_text, ld_dwv, ld_dwt, db_video, db_text, stream);
-        case CROSSCLR_IN_F16: return project_dw_t<in_f16>(b, D, gy_video, gy_text, ld_gy, x_video, x_text, ld_xv, ld_xt, Din_video, Din_text, ws, dw_video, dw_text, ld_dwv, ld_dwt, db_video, db_text, stream);
-        case CROSSCLR_IN_BF16: return project_dw_t<in_bf16>(b, D, gy_video, gy_text, ld_gy, x_video, x_text, ld_xv, ld_xt, Din_video, Din_text, ws, dw_video, dw_text, ld_dwv, ld_dwt, db_video, db_text, stream);
-    }
-    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
+    return with_in_dtype(in_dtype, [&](auto tin) {
+        return project_dw_t<typename decltype(tin)::type>(b, D, gy_video, gy_text, ld_gy, x_video, x_text, ld_xv, ld_xt, Din_video, Din_text, ws, dw_video,
+                                                          dw_text, ld_dwv, ld_dwt, db_video, db_text, stream);
+    });
 }
 
 extern "C" int crossclr_project_backward_prep(const crossclr_plan* plan, const float* g_video, const float* g_text, long ld_gv,
@@ -1362,13 +1358,10 @@ extern "C" int crossclr_backward_finish_p(const crossclr_plan* plan, const float
     if (!plan || !gbuf || !video || !text || !inv_norm || !grad_out || !grad_video || !grad_text)
         return fail(CROSSCLR_E_ARG, "NULL argument");
     if (!(temperature > 0.f)) return fail(CROSSCLR_E_ARG, "temperature must be > 0");
-    switch (in_dtype) {
-        case CROSSCLR_IN_F32: return backward_finish_t<float>(plan, gbuf, video, text, ld_video, ld_text, inv_norm, temperature, grad_out, grad_video, grad_text, ld_gvideo, ld_gtext, lw, stream, prenormalized);
-        case CROSSCLR_IN_F64: return backward_finish_t<double>(plan, gbuf, video, text, ld_video, ld_text, inv_norm, temperature, grad_out, grad_video, grad_text, ld_gvideo, ld_gtext, lw, stream, prenormalized);
-        case CROSSCLR_IN_F16: return backward_finish_t<in_f16>(plan, gbuf, video, text, ld_video, ld_text, inv_norm, temperature, grad_out, grad_video, grad_text, ld_gvideo, ld_gtext, lw, stream, prenormalized);
-        case CROSSCLR_IN_BF16: return backward_finish_t<in_bf16>(plan, gbuf, video, text, ld_video, ld_text, inv_norm, temperature, grad_out, grad_video, grad_text, ld_gvideo, ld_gtext, lw, stream, prenormalized);
-    }
-    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
+    return with_in_dtype(in_dtype, [&](auto tin) {
+        return backward_finish_t<typename decltype(tin)::type>(plan, gbuf, video, text, ld_video, ld_text, inv_norm, temperature, grad_out, grad_video,
+                                                               grad_text, ld_gvideo, ld_gtext, lw, stream, prenormalized);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1527,13 +1520,8 @@ extern "C" int crossclr_topk_pack(const void* x, long ld, int rows, int D, int i
     if (int rc = topk_set_ok("crossclr_topk_pack", rows, D)) return rc;
     if (!topk_mode_ok(mode)) return fail(CROSSCLR_E_ARG, "bad mode %d", mode);
     if (ld < D) return fail(CROSSCLR_E_ARG, "row stride smaller than D");
-    switch (in_dtype) {
-        case CROSSCLR_IN_F32: return topk_pack_t<float>(x, ld, rows, D, mode, normalize, packed, stream);
-        case CROSSCLR_IN_F64: return topk_pack_t<double>(x, ld, rows, D, mode, normalize, packed, stream);
-        case CROSSCLR_IN_F16: return topk_pack_t<in_f16>(x, ld, rows, D, mode, normalize, packed, stream);
-        case CROSSCLR_IN_BF16: return topk_pack_t<in_bf16>(x, ld, rows, D, mode, normalize, packed, stream);
-    }
-    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
+    return with_in_dtype(in_dtype,
+                         [&](auto tin) { return topk_pack_t<typename decltype(tin)::type>(x, ld, rows, D, mode, normalize, packed, stream); });
 }
 extern "C" int crossclr_topk_splits(int nq, int ng, int k, int requested) {
     if (int rc = topk_args_ok("crossclr_topk_splits", nq, ng, 1, k)) return rc;
@@ -1666,13 +1654,10 @@ extern "C" int crossclr_hardneg_backward(const crossclr_plan* plan, const void* 
     if (!im || !s || !best_index || !hinge || !grad_out || (!grad_im && !grad_s)) return fail(CROSSCLR_E_ARG, "NULL argument");
     if (ld_im < plan->D || ld_s < plan->D || (grad_im && ld_gim < plan->D) || (grad_s && ld_gs < plan->D))
         return fail(CROSSCLR_E_ARG, "row stride smaller than D");
-    switch (in_dtype) {
-        case CROSSCLR_IN_F32: return hardneg_backward_t<float>(plan, im, s, ld_im, ld_s, best_index, hinge, grad_out, grad_im, grad_s, ld_gim, ld_gs, stream);
-        case CROSSCLR_IN_F64: return hardneg_backward_t<double>(plan, im, s, ld_im, ld_s, best_index, hinge, grad_out, grad_im, grad_s, ld_gim, ld_gs, stream);
-        case CROSSCLR_IN_F16: return hardneg_backward_t<in_f16>(plan, im, s, ld_im, ld_s, best_index, hinge, grad_out, grad_im, grad_s, ld_gim, ld_gs, stream);
-        case CROSSCLR_IN_BF16: return hardneg_backward_t<in_bf16>(plan, im, s, ld_im, ld_s, best_index, hinge, grad_out, grad_im, grad_s, ld_gim, ld_gs, stream);
-    }
-    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
+    return with_in_dtype(in_dtype, [&](auto tin) {
+        return hardneg_backward_t<typename decltype(tin)::type>(plan, im, s, ld_im, ld_s, best_index, hinge, grad_out, grad_im, grad_s, ld_gim, ld_gs,
+                                                                stream);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1751,24 +1736,52 @@ extern "C" int crossclr_infonce_finish(const crossclr_plan* plan, const void* wo
     LAUNCH(fwd_finish_reduce_kernel, dim3(1), dim3(64), stream, loss_sum, nb, 0.5 / (double)plan->b);
     return launch_status("infonce_finish_kernel");
 }
-static int infonce_backward(const char* what, const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* lse,
-                            const float* pair_score, const int32_t* group, float* gbuf, void* stream) {
+// The gradient product of the InfoNCE and the sigmoid loss (two kernels on one skeleton): the checks, the tiles per slice, the operand type
+// and DC are the same for both; launch(type_tag<T>(), std::integral_constant<int, DC>(), tps) starts the loss's own kernel.
+template <class F>
+static int pairloss_backward(const char* what, const crossclr_plan* plan, bool args_ok, float* gbuf, const char* label, F launch) {
     if (int rc = hardneg_plan_ok(what, plan)) return rc;
-    if (!xhat || !logit_scale || !lse || !pair_score || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
+    if (!args_ok || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
     if (plan->bwd_slices < 1) return fail(CROSSCLR_E_ARG, "bad plan");
     const int tps = (plan->bpad / 64 + plan->bwd_slices - 1) / plan->bwd_slices;
     return with_plan_type(plan, [&](auto t) {
+        with_d_chunk<256, 128, 64>(plan->Dpad, [&](auto dc) { launch(t, dc, tps); });
+        return launch_status(label);
+    });
+}
+// The gradient finish of both: g = s / (per_b B) M_p (per_b = 2 for InfoNCE, 1 for the sigmoid loss), dscale[0] = grad_out * sum_p <x^_p, M_p>
+// over the 2 B stacked rows (= 2 sum_ij W S), dscale[1] = that times reduce_num / B = grad_out * dL/ds (1 / (4 B) and 1 / (2 B))
+static int pairloss_backward_finish(const char* what, const crossclr_plan* plan, const float* gbuf, const void* video, const void* text,
+                                    long ld_video, long ld_text, int in_dtype, const float* inv_norm, int normalized, const float* logit_scale,
+                                    const double* grad_out, void* grad_video, void* grad_text, long ld_gvideo, long ld_gtext, double* dscale,
+                                    double per_b, double reduce_num, void* stream) {
+    if (int rc = hardneg_plan_ok(what, plan)) return rc;
+    if (!gbuf || !video || !text || !logit_scale || !grad_out || !dscale || (normalized && !inv_norm)) return fail(CROSSCLR_E_ARG, "NULL argument");
+    if (plan->bwd_slices < 1 || plan->loss_ws_doubles < 2) return fail(CROSSCLR_E_ARG, "bad plan");
+    if (ld_video < plan->D || ld_text < plan->D || (grad_video && ld_gvideo < plan->D) || (grad_text && ld_gtext < plan->D))
+        return fail(CROSSCLR_E_ARG, "row stride smaller than D");
+    const int nb = plan->loss_ws_doubles - 1;
+    return with_in_dtype(in_dtype, [&](auto tin) {
+        using TIN = typename decltype(tin)::type;
+        LAUNCH((pairloss_backward_finish_kernel<TIN>), dim3(nb), dim3(256), stream, gbuf, plan->bwd_slices, (const TIN*)video, (const TIN*)text,
+               ld_video, ld_text, plan->b, plan->bpad, plan->D, plan->Dpad, inv_norm, normalized, logit_scale, per_b * (double)plan->b, grad_out, (TIN*)grad_video,
+               (TIN*)grad_text, ld_gvideo, ld_gtext, dscale);
+        LAUNCH(fwd_finish_reduce_kernel, dim3(1), dim3(64), stream, dscale, nb, reduce_num / (double)plan->b);
+        return launch_status("pairloss_backward_finish_kernel");
+    });
+}
+static int infonce_backward(const char* what, const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* lse,
+                            const float* pair_score, const int32_t* group, float* gbuf, void* stream) {
+    return pairloss_backward(what, plan, xhat && logit_scale && lse && pair_score, gbuf,
+                             group ? "infonce_backward_kernel<IDS>" : "infonce_backward_kernel", [&](auto t, auto dc, int tps) {
         using T = typename decltype(t)::type;
-        with_d_chunk<256, 128, 64>(plan->Dpad, [&](auto dc) {
-            constexpr int DC = decltype(dc)::value;
-            if (group)
-                LAUNCH((infonce_backward_kernel<T, DC, true, const int*>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad,
-                       logit_scale, lse, pair_score, gbuf, tps, (const int*)group);
-            else
-                LAUNCH((infonce_backward_kernel<T, DC>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad,
-                       logit_scale, lse, pair_score, gbuf, tps);
-        });
-        return launch_status(group ? "infonce_backward_kernel<IDS>" : "infonce_backward_kernel");
+        constexpr int DC = decltype(dc)::value;
+        if (group)
+            LAUNCH((infonce_backward_kernel<T, DC, true, const int*>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad,
+                   logit_scale, lse, pair_score, gbuf, tps, (const int*)group);
+        else
+            LAUNCH((infonce_backward_kernel<T, DC>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad,
+                   logit_scale, lse, pair_score, gbuf, tps);
     });
 }
 extern "C" int crossclr_infonce_backward(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* lse,
@@ -1780,36 +1793,12 @@ extern "C" int crossclr_infonce_backward_ids(const crossclr_plan* plan, const vo
     if (!group) return fail(CROSSCLR_E_ARG, "crossclr_infonce_backward_ids: group is NULL (crossclr_pair_groups)");
     return infonce_backward("crossclr_infonce_backward_ids", plan, xhat, logit_scale, lse, pair_score, group, gbuf, stream);
 }
-template <typename TIN>
-static int infonce_backward_finish_t(const crossclr_plan* p, const float* gbuf, const void* video, const void* text, long ldv, long ldt,
-                                     const float* inv_norm, int normalized, const float* logit_scale, const double* grad_out, void* gvideo,
-                                     void* gtext, long ldgv, long ldgt, double* dscale, void* stream) {
-    const int nb = p->loss_ws_doubles - 1;
-    LAUNCH((infonce_backward_finish_kernel<TIN>), dim3(nb), dim3(256), stream, gbuf, p->bwd_slices, (const TIN*)video, (const TIN*)text, ldv, ldt,
-           p->b, p->bpad, p->D, p->Dpad, inv_norm, normalized, logit_scale, grad_out, (TIN*)gvideo, (TIN*)gtext, ldgv, ldgt, dscale);
-    // dscale[0] = grad_out * sum_p <x^_p, M_p> over the 2 B stacked rows (= 2 sum_ij W S), dscale[1] = that / (4 B) = grad_out * dL/ds
-    LAUNCH(fwd_finish_reduce_kernel, dim3(1), dim3(64), stream, dscale, nb, 0.25 / (double)p->b);
-    return launch_status("infonce_backward_finish_kernel");
-}
 extern "C" int crossclr_infonce_backward_finish(const crossclr_plan* plan, const float* gbuf, const void* video, const void* text, long ld_video,
                                                 long ld_text, int in_dtype, const float* inv_norm, int normalized, const float* logit_scale,
                                                 const double* grad_out, void* grad_video, void* grad_text, long ld_gvideo, long ld_gtext,
                                                 double* dscale, void* stream) {
-    if (int rc = hardneg_plan_ok("crossclr_infonce_backward_finish", plan)) return rc;
-    if (!gbuf || !video || !text || !logit_scale || !grad_out || !dscale || (normalized && !inv_norm)) return fail(CROSSCLR_E_ARG, "NULL argument");
-    if (plan->bwd_slices < 1 || plan->loss_ws_doubles < 2) return fail(CROSSCLR_E_ARG, "bad plan");
-    if (ld_video < plan->D || ld_text < plan->D || (grad_video && ld_gvideo < plan->D) || (grad_text && ld_gtext < plan->D))
-        return fail(CROSSCLR_E_ARG, "row stride smaller than D");
-#define CROSSCLR_IBF(TIN) infonce_backward_finish_t<TIN>(plan, gbuf, video, text, ld_video, ld_text, inv_norm, normalized, logit_scale, grad_out, \
-                                                         grad_video, grad_text, ld_gvideo, ld_gtext, dscale, stream)
-    switch (in_dtype) {
-        case CROSSCLR_IN_F32: return CROSSCLR_IBF(float);
-        case CROSSCLR_IN_F64: return CROSSCLR_IBF(double);
-        case CROSSCLR_IN_F16: return CROSSCLR_IBF(in_f16);
-        case CROSSCLR_IN_BF16: return CROSSCLR_IBF(in_bf16);
-    }
-#undef CROSSCLR_IBF
-    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
+    return pairloss_backward_finish("crossclr_infonce_backward_finish", plan, gbuf, video, text, ld_video, ld_text, in_dtype, inv_norm, normalized,
+                                    logit_scale, grad_out, grad_video, grad_text, ld_gvideo, ld_gtext, dscale, 2.0, 0.25, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1881,22 +1870,16 @@ extern "C" int crossclr_sigmoid_finish(const crossclr_plan* plan, const void* wo
 }
 static int sigmoid_backward(const char* what, const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias,
                             const int32_t* group, float* gbuf, void* stream) {
-    if (int rc = hardneg_plan_ok(what, plan)) return rc;
-    if (!xhat || !logit_scale || !logit_bias || !gbuf) return fail(CROSSCLR_E_ARG, "NULL argument");
-    if (plan->bwd_slices < 1) return fail(CROSSCLR_E_ARG, "bad plan");
-    const int tps = (plan->bpad / 64 + plan->bwd_slices - 1) / plan->bwd_slices;
-    return with_plan_type(plan, [&](auto t) {
+    return pairloss_backward(what, plan, xhat && logit_scale && logit_bias, gbuf,
+                             group ? "sigmoid_backward_kernel<IDS>" : "sigmoid_backward_kernel", [&](auto t, auto dc, int tps) {
         using T = typename decltype(t)::type;
-        with_d_chunk<256, 128, 64>(plan->Dpad, [&](auto dc) {
-            constexpr int DC = decltype(dc)::value;
-            if (group)
-                LAUNCH((sigmoid_backward_kernel<T, DC, true, const int*>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad,
-                       logit_scale, logit_bias, gbuf, tps, (const int*)group);
-            else
-                LAUNCH((sigmoid_backward_kernel<T, DC>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad,
-                       logit_scale, logit_bias, gbuf, tps);
-        });
-        return launch_status(group ? "sigmoid_backward_kernel<IDS>" : "sigmoid_backward_kernel");
+        constexpr int DC = decltype(dc)::value;
+        if (group)
+            LAUNCH((sigmoid_backward_kernel<T, DC, true, const int*>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad,
+                   logit_scale, logit_bias, gbuf, tps, (const int*)group);
+        else
+            LAUNCH((sigmoid_backward_kernel<T, DC>), bwd_grid(plan, DC), dim3(256), stream, (const T*)xhat, plan->b, plan->bpad, plan->Dpad,
+                   logit_scale, logit_bias, gbuf, tps);
     });
 }
 extern "C" int crossclr_sigmoid_backward(const crossclr_plan* plan, const void* xhat, const float* logit_scale, const float* logit_bias,
@@ -1908,36 +1891,12 @@ extern "C" int crossclr_sigmoid_backward_ids(const crossclr_plan* plan, const vo
     if (!group) return fail(CROSSCLR_E_ARG, "crossclr_sigmoid_backward_ids: group is NULL (crossclr_pair_groups)");
     return sigmoid_backward("crossclr_sigmoid_backward_ids", plan, xhat, logit_scale, logit_bias, group, gbuf, stream);
 }
-template <typename TIN>
-static int sigmoid_backward_finish_t(const crossclr_plan* p, const float* gbuf, const void* video, const void* text, long ldv, long ldt,
-                                     const float* inv_norm, int normalized, const float* logit_scale, const double* grad_out, void* gvideo,
-                                     void* gtext, long ldgv, long ldgt, double* dscale, void* stream) {
-    const int nb = p->loss_ws_doubles - 1;
-    LAUNCH((sigmoid_backward_finish_kernel<TIN>), dim3(nb), dim3(256), stream, gbuf, p->bwd_slices, (const TIN*)video, (const TIN*)text, ldv, ldt,
-           p->b, p->bpad, p->D, p->Dpad, inv_norm, normalized, logit_scale, grad_out, (TIN*)gvideo, (TIN*)gtext, ldgv, ldgt, dscale);
-    // dscale[0] = grad_out * sum_p <x^_p, M_p> over the 2 B stacked rows (= 2 sum_ij W S), dscale[1] = that / (2 B) = grad_out * dL/ds
-    LAUNCH(fwd_finish_reduce_kernel, dim3(1), dim3(64), stream, dscale, nb, 0.5 / (double)p->b);
-    return launch_status("sigmoid_backward_finish_kernel");
-}
 extern "C" int crossclr_sigmoid_backward_finish(const crossclr_plan* plan, const float* gbuf, const void* video, const void* text, long ld_video,
                                                 long ld_text, int in_dtype, const float* inv_norm, int normalized, const float* logit_scale,
                                                 const double* grad_out, void* grad_video, void* grad_text, long ld_gvideo, long ld_gtext,
                                                 double* dscale, void* stream) {
-    if (int rc = hardneg_plan_ok("crossclr_sigmoid_backward_finish", plan)) return rc;
-    if (!gbuf || !video || !text || !logit_scale || !grad_out || !dscale || (normalized && !inv_norm)) return fail(CROSSCLR_E_ARG, "NULL argument");
-    if (plan->bwd_slices < 1 || plan->loss_ws_doubles < 2) return fail(CROSSCLR_E_ARG, "bad plan");
-    if (ld_video < plan->D || ld_text < plan->D || (grad_video && ld_gvideo < plan->D) || (grad_text && ld_gtext < plan->D))
-        return fail(CROSSCLR_E_ARG, "row stride smaller than D");
-#define CROSSCLR_SBF(TIN) sigmoid_backward_finish_t<TIN>(plan, gbuf, video, text, ld_video, ld_text, inv_norm, normalized, logit_scale, grad_out, \
-                                                         grad_video, grad_text, ld_gvideo, ld_gtext, dscale, stream)
-    switch (in_dtype) {
-        case CROSSCLR_IN_F32: return CROSSCLR_SBF(float);
-        case CROSSCLR_IN_F64: return CROSSCLR_SBF(double);
-        case CROSSCLR_IN_F16: return CROSSCLR_SBF(in_f16);
-        case CROSSCLR_IN_BF16: return CROSSCLR_SBF(in_bf16);
-    }
-#undef CROSSCLR_SBF
-    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
+    return pairloss_backward_finish("crossclr_sigmoid_backward_finish", plan, gbuf, video, text, ld_video, ld_text, in_dtype, inv_norm, normalized,
+                                    logit_scale, grad_out, grad_video, grad_text, ld_gvideo, ld_gtext, dscale, 1.0, 0.5, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1974,13 +1933,9 @@ extern "C" int crossclr_influence_colsum(const void* x_video, const void* x_text
     static_assert(kInflBlocks == CROSSCLR_INFL_BLOCKS && 256 * kInflMaxCols == CROSSCLR_INFL_MAX_DIN, "header out of sync");
     if (int rc = infl_args(x_video, x_text, ld_video, ld_text, b, Din)) return rc;
     if (!inv_norm || !partial_ws || !colsum) return fail(CROSSCLR_E_ARG, "NULL argument");
-    switch (in_dtype) {
-        case CROSSCLR_IN_F32: return infl_colsum_t<float>(x_video, x_text, ld_video, ld_text, b, Din, inv_norm, partial_ws, colsum, stream);
-        case CROSSCLR_IN_F64: return infl_colsum_t<double>(x_video, x_text, ld_video, ld_text, b, Din, inv_norm, partial_ws, colsum, stream);
-        case CROSSCLR_IN_F16: return infl_colsum_t<in_f16>(x_video, x_text, ld_video, ld_text, b, Din, inv_norm, partial_ws, colsum, stream);
-        case CROSSCLR_IN_BF16: return infl_colsum_t<in_bf16>(x_video, x_text, ld_video, ld_text, b, Din, inv_norm, partial_ws, colsum, stream);
-    }
-    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
+    return with_in_dtype(in_dtype, [&](auto tin) {
+        return infl_colsum_t<typename decltype(tin)::type>(x_video, x_text, ld_video, ld_text, b, Din, inv_norm, partial_ws, colsum, stream);
+    });
 }
 
 extern "C" int crossclr_influence_conn(const void* x_video, const void* x_text, long ld_video, long ld_text, int in_dtype,
@@ -1988,13 +1943,9 @@ extern "C" int crossclr_influence_conn(const void* x_video, const void* x_text, 
                                        double* conn, void* stream) {
     if (int rc = infl_args(x_video, x_text, ld_video, ld_text, b, Din)) return rc;
     if (!inv_norm || !colsum_total || !conn || B_global < b) return fail(CROSSCLR_E_ARG, "NULL argument / B_global < b");
-    switch (in_dtype) {
-        case CROSSCLR_IN_F32: return infl_conn_t<float>(x_video, x_text, ld_video, ld_text, b, Din, inv_norm, colsum_total, B_global, conn, stream);
-        case CROSSCLR_IN_F64: return infl_conn_t<double>(x_video, x_text, ld_video, ld_text, b, Din, inv_norm, colsum_total, B_global, conn, stream);
-        case CROSSCLR_IN_F16: return infl_conn_t<in_f16>(x_video, x_text, ld_video, ld_text, b, Din, inv_norm, colsum_total, B_global, conn, stream);
-        case CROSSCLR_IN_BF16: return infl_conn_t<in_bf16>(x_video, x_text, ld_video, ld_text, b, Din, inv_norm, colsum_total, B_global, conn, stream);
-    }
-    return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
+    return with_in_dtype(in_dtype, [&](auto tin) {
+        return infl_conn_t<typename decltype(tin)::type>(x_video, x_text, ld_video, ld_text, b, Din, inv_norm, colsum_total, B_global, conn, stream);
+    });
 }
 
 extern "C" int crossclr_influence_finish(const crossclr_plan* plan, const double* conn_all, float score_threshold,
@@ -2429,17 +2380,12 @@ extern "C" int crossclr_second_order(const crossclr_plan* plan, const void* vide
                                  F(H.gbuf1), 0, stream);
     }
     if (rc) return rc;
-    switch (in_dtype) {
-#define CROSSCLR_SO(TIN) second_order_impl<TIN>(plan, H, g, (const TIN*)video, (const TIN*)text, ld_video, ld_text, temperature, negative_weight, k, lw, \
-                                                prenormalized, two_pass, (const TIN*)u_video, (const TIN*)u_text, ld_uvideo, ld_utext, grad_out, w,       \
-                                                (TIN*)h_video, (TIN*)h_text, ld_hvideo, ld_htext, d_grad_out, stream)
-        case CROSSCLR_IN_F32: return CROSSCLR_SO(float);
-        case CROSSCLR_IN_F64: return CROSSCLR_SO(double);
-        case CROSSCLR_IN_F16: return CROSSCLR_SO(in_f16);
-        case CROSSCLR_IN_BF16: return CROSSCLR_SO(in_bf16);
-#undef CROSSCLR_SO
-        default: return fail(CROSSCLR_E_ARG, "bad in_dtype %d", in_dtype);
-    }
+    return with_in_dtype(in_dtype, [&](auto tin) {
+        using TIN = typename decltype(tin)::type;
+        return second_order_impl<TIN>(plan, H, g, (const TIN*)video, (const TIN*)text, ld_video, ld_text, temperature, negative_weight, k, lw,
+                                      prenormalized, two_pass, (const TIN*)u_video, (const TIN*)u_text, ld_uvideo, ld_utext, grad_out, w,
+                                      (TIN*)h_video, (TIN*)h_text, ld_hvideo, ld_htext, d_grad_out, stream);
+    });
 }
 
 extern "C" int crossclr_mfma_sustained(float* out, int blocks, int iters, unsigned seed, int zero_operands, void* stream) {

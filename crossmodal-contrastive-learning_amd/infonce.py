@@ -57,6 +57,50 @@ def _pair_groups(pair_ids: torch.Tensor, plan, stream) -> torch.Tensor:
     return group
 
 
+def _lay_out(plan, video: torch.Tensor, text: torch.Tensor, normalize: bool, stream):
+    """The packed operand of both rows (crossclr_normalize, or crossclr_pack for rows taken as given) -> in_dtype, xhat, inv_norm [2 bpad]"""
+    lib = nat.library()
+    f32 = dict(dtype=torch.float32, device=video.device)
+    in_dtype = _IN_DTYPE[video.dtype]
+    xhat = torch.empty(plan.operand_bytes, dtype=torch.uint8, device=video.device)
+    inv_norm, pair_cos = torch.empty(2 * plan.bpad, **f32), torch.empty(plan.bpad, **f32)
+    lay_out = lib.crossclr_normalize if normalize else lib.crossclr_pack
+    nat.check(lay_out(ctypes.byref(plan), _ptr(video), _ptr(text), video.stride(0), text.stride(0), in_dtype, _ptr(xhat), _ptr(inv_norm),
+                      _ptr(pair_cos), stream))
+    return in_dtype, xhat, inv_norm
+
+
+def _scalar(value, name: str, like: torch.Tensor) -> torch.Tensor:
+    """a float -> a one-element fp32 tensor on the inputs' device; a tensor is checked and handed on"""
+    if isinstance(value, torch.Tensor):
+        if value.numel() != 1 or not value.is_floating_point():
+            raise RuntimeError(f"{name} must be a float or a one-element float tensor, got shape {tuple(value.shape)} "
+                               f"and dtype {value.dtype}")
+        if value.device != like.device:
+            raise RuntimeError(f"{name} is on {value.device}, the inputs are on {like.device}")
+        return value
+    return torch.full((1,), float(value), dtype=torch.float32, device=like.device)
+
+
+def _refuse_auto(what: str, compute_mode: str) -> None:
+    if compute_mode == "auto":
+        raise ValueError(f"{what}: compute_mode='auto' is not offered (at a logit scale of 100 bf16 operands have no a-priori error "
+                         "bar); pass 'fp32', 'bf16x3' or 'bf16'")
+
+
+def _gradient_finish(finish, ctx, gbuf, v_c, t_c, inv_norm, scale32, go, stream):
+    """The row finish of a gradient product (`finish`: crossclr_infonce_backward_finish or crossclr_sigmoid_backward_finish) ->
+    (g_v, g_t, dscale): the input gradients ctx.needs_input_grad asks for (else None) and dscale [loss_ws_doubles], [1] = grad_out dL/ds"""
+    need, plan = ctx.needs_input_grad, ctx.plan
+    g_v = torch.empty_like(v_c) if need[0] else None
+    g_t = torch.empty_like(t_c) if need[1] else None
+    dscale = torch.empty(plan.loss_ws_doubles, dtype=torch.float64, device=v_c.device)
+    nat.check(finish(ctypes.byref(plan), _ptr(gbuf), _ptr(v_c), _ptr(t_c), v_c.stride(0), t_c.stride(0), ctx.in_dtype, _ptr(inv_norm),
+                     int(ctx.normalize), _ptr(scale32), _ptr(go), _ptr(g_v), _ptr(g_t), 0 if g_v is None else g_v.stride(0),
+                     0 if g_t is None else g_t.stride(0), _ptr(dscale), stream))
+    return g_v, g_t, dscale
+
+
 class _Stats:
     __slots__ = ("plan", "in_dtype", "xhat", "inv_norm", "lse", "pair", "loss_sum", "group")
 
@@ -74,12 +118,8 @@ def _stats(video: torch.Tensor, text: torch.Tensor, scale32: torch.Tensor, mode:
     stream = _stream_for(video)
     f32 = dict(dtype=torch.float32, device=dev)
     st = _Stats()
-    st.plan, st.in_dtype = plan, _IN_DTYPE[video.dtype]
-    st.xhat = torch.empty(plan.operand_bytes, dtype=torch.uint8, device=dev)
-    st.inv_norm, pair_cos = torch.empty(2 * plan.bpad, **f32), torch.empty(plan.bpad, **f32)
-    lay_out = lib.crossclr_normalize if normalize else lib.crossclr_pack
-    nat.check(lay_out(pp, _ptr(video), _ptr(text), video.stride(0), text.stride(0), st.in_dtype, _ptr(st.xhat), _ptr(st.inv_norm),
-                      _ptr(pair_cos), stream))
+    st.plan = plan
+    st.in_dtype, st.xhat, st.inv_norm = _lay_out(plan, video, text, normalize, stream)
     ws = torch.empty(lib.crossclr_infonce_workspace_bytes(pp, splits), dtype=torch.uint8, device=dev)
     st.group = None if pair_ids is None else _pair_groups(pair_ids, plan, stream)
     if st.group is None:
@@ -114,7 +154,6 @@ class _InfoNCEFunction(torch.autograd.Function):
         v_c, t_c, xhat, inv_norm, lse, pair, scale32, group = ctx.saved_tensors
         lib, plan, dev = nat.library(), ctx.plan, v_c.device
         pp = ctypes.byref(plan)
-        need = ctx.needs_input_grad
         with _device_of(v_c):
             stream = _stream_for(v_c)
             gbuf = torch.empty(plan.gbuf_bytes // 4, dtype=torch.float32, device=dev)
@@ -124,15 +163,9 @@ class _InfoNCEFunction(torch.autograd.Function):
                 nat.check(lib.crossclr_infonce_backward_ids(pp, _ptr(xhat), _ptr(scale32), _ptr(lse), _ptr(pair), _ptr(group), _ptr(gbuf),
                                                             stream))
             go = grad_out.detach().to(device=dev, dtype=torch.float64).reshape(1).contiguous()
-            g_v = torch.empty_like(v_c) if need[0] else None
-            g_t = torch.empty_like(t_c) if need[1] else None
-            dscale = torch.empty(plan.loss_ws_doubles, dtype=torch.float64, device=dev)
-            nat.check(lib.crossclr_infonce_backward_finish(pp, _ptr(gbuf), _ptr(v_c), _ptr(t_c), v_c.stride(0), t_c.stride(0), ctx.in_dtype,
-                                                           _ptr(inv_norm), int(ctx.normalize), _ptr(scale32), _ptr(go), _ptr(g_v), _ptr(g_t),
-                                                           0 if g_v is None else g_v.stride(0), 0 if g_t is None else g_t.stride(0),
-                                                           _ptr(dscale), stream))
+            g_v, g_t, dscale = _gradient_finish(lib.crossclr_infonce_backward_finish, ctx, gbuf, v_c, t_c, inv_norm, scale32, go, stream)
             g_s = None
-            if need[2]:
+            if ctx.needs_input_grad[2]:
                 shape, dtype = ctx.scale_meta
                 g_s = dscale[1].reshape(shape).to(dtype)
         return g_v, g_t, g_s, None, None, None, None
@@ -143,19 +176,9 @@ def _info_nce(video: torch.Tensor, text: torch.Tensor, logit_scale, normalize: b
     domain (value, remainder), pair_score [bpad])."""
     _check(video, text)
     pair_ids = _checked_pair_ids(pair_ids, video)
-    if compute_mode == "auto":
-        raise ValueError("info_nce_loss: compute_mode='auto' is not offered (at a logit scale of 100 bf16 operands have no a-priori error "
-                         "bar); pass 'fp32', 'bf16x3' or 'bf16'")
+    _refuse_auto("info_nce_loss", compute_mode)
     mode = _resolve_mode(compute_mode, video.shape[0], video.dtype)
-    if isinstance(logit_scale, torch.Tensor):
-        if logit_scale.numel() != 1 or not logit_scale.is_floating_point():
-            raise RuntimeError(f"logit_scale must be a float or a one-element float tensor, got shape {tuple(logit_scale.shape)} "
-                               f"and dtype {logit_scale.dtype}")
-        if logit_scale.device != video.device:
-            raise RuntimeError(f"logit_scale is on {logit_scale.device}, the inputs are on {video.device}")
-        scale = logit_scale
-    else:
-        scale = torch.full((1,), float(logit_scale), dtype=torch.float32, device=video.device)
+    scale = _scalar(logit_scale, "logit_scale", video)
     return _InfoNCEFunction.apply(video, text, scale, bool(normalize), mode, int(splits), pair_ids)
 
 

@@ -26,8 +26,8 @@ import torch
 from torch import nn
 
 from . import _native as nat
-from .infonce import _checked_pair_ids, _pair_groups
-from .loss import _IN_DTYPE, _device_of, _plan_for, _ptr, _refuse_double_backward, _resolve_mode, _row_major, _stream_for
+from .infonce import _checked_pair_ids, _gradient_finish, _lay_out, _pair_groups, _refuse_auto, _scalar
+from .loss import _device_of, _plan_for, _ptr, _refuse_double_backward, _resolve_mode, _row_major, _stream_for
 from .ranking import _check
 
 
@@ -49,12 +49,7 @@ class _SigmoidFunction(torch.autograd.Function):
             stream = _stream_for(v_c)
             scale32 = scale.detach().reshape(1).to(torch.float32)      # (device ops: the values stay where they are)
             bias32 = bias.detach().reshape(1).to(torch.float32)
-            in_dtype = _IN_DTYPE[v_c.dtype]
-            xhat = torch.empty(plan.operand_bytes, dtype=torch.uint8, device=dev)
-            inv_norm, pair_cos = torch.empty(2 * plan.bpad, **f32), torch.empty(plan.bpad, **f32)
-            lay_out = lib.crossclr_normalize if normalize else lib.crossclr_pack
-            nat.check(lay_out(pp, _ptr(v_c), _ptr(t_c), v_c.stride(0), t_c.stride(0), in_dtype, _ptr(xhat), _ptr(inv_norm), _ptr(pair_cos),
-                              stream))
+            in_dtype, xhat, inv_norm = _lay_out(plan, v_c, t_c, normalize, stream)
             ws = torch.empty(lib.crossclr_sigmoid_workspace_bytes(pp, splits), dtype=torch.uint8, device=dev)
             group = None if pair_ids is None else _pair_groups(pair_ids, plan, stream)      # once: the backward reads the same array
             if group is None:
@@ -92,13 +87,7 @@ class _SigmoidFunction(torch.autograd.Function):
                     nat.check(lib.crossclr_sigmoid_backward(pp, _ptr(xhat), _ptr(scale32), _ptr(bias32), _ptr(gbuf), stream))
                 else:
                     nat.check(lib.crossclr_sigmoid_backward_ids(pp, _ptr(xhat), _ptr(scale32), _ptr(bias32), _ptr(group), _ptr(gbuf), stream))
-                g_v = torch.empty_like(v_c) if need[0] else None
-                g_t = torch.empty_like(t_c) if need[1] else None
-                dscale = torch.empty(plan.loss_ws_doubles, dtype=torch.float64, device=dev)
-                nat.check(lib.crossclr_sigmoid_backward_finish(pp, _ptr(gbuf), _ptr(v_c), _ptr(t_c), v_c.stride(0), t_c.stride(0), ctx.in_dtype,
-                                                               _ptr(inv_norm), int(ctx.normalize), _ptr(scale32), _ptr(go), _ptr(g_v), _ptr(g_t),
-                                                               0 if g_v is None else g_v.stride(0), 0 if g_t is None else g_t.stride(0),
-                                                               _ptr(dscale), stream))
+                g_v, g_t, dscale = _gradient_finish(lib.crossclr_sigmoid_backward_finish, ctx, gbuf, v_c, t_c, inv_norm, scale32, go, stream)
                 if need[2]:
                     shape, dtype = ctx.scale_meta
                     g_s = dscale[1].reshape(shape).to(dtype)
@@ -108,27 +97,13 @@ class _SigmoidFunction(torch.autograd.Function):
         return g_v, g_t, g_s, g_b, None, None, None, None
 
 
-def _scalar(value, name: str, like: torch.Tensor) -> torch.Tensor:
-    """a float -> a one-element fp32 tensor on the inputs' device; a tensor is checked and handed on"""
-    if isinstance(value, torch.Tensor):
-        if value.numel() != 1 or not value.is_floating_point():
-            raise RuntimeError(f"{name} must be a float or a one-element float tensor, got shape {tuple(value.shape)} "
-                               f"and dtype {value.dtype}")
-        if value.device != like.device:
-            raise RuntimeError(f"{name} is on {value.device}, the inputs are on {like.device}")
-        return value
-    return torch.full((1,), float(value), dtype=torch.float32, device=like.device)
-
-
 def _sigmoid(video: torch.Tensor, text: torch.Tensor, logit_scale, logit_bias, normalize: bool, compute_mode: str, splits: int = 0,
              pair_ids=None):
     """`sigmoid_loss` with the number of column splits exposed (0 = the library's choice); returns (loss, row_loss [bpad] in nats -- row
     i's share of B L, 0 for padding entries --, pair_score [bpad])."""
     _check(video, text)
     pair_ids = _checked_pair_ids(pair_ids, video)
-    if compute_mode == "auto":
-        raise ValueError("sigmoid_loss: compute_mode='auto' is not offered (at a logit scale of 100 bf16 operands have no a-priori error "
-                         "bar); pass 'fp32', 'bf16x3' or 'bf16'")
+    _refuse_auto("sigmoid_loss", compute_mode)
     mode = _resolve_mode(compute_mode, video.shape[0], video.dtype)
     scale, bias = _scalar(logit_scale, "logit_scale", video), _scalar(logit_bias, "logit_bias", video)
     return _SigmoidFunction.apply(video, text, scale, bias, bool(normalize), mode, int(splits), pair_ids)

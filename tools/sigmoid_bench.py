@@ -7,7 +7,7 @@ quantity; the median per quantity), so that clock and box drift fall on both sid
   forward    crossclr_sigmoid_stats + crossclr_sigmoid_finish   against   crossclr_infonce_stats + crossclr_infonce_finish (the same
              2 B^2 D product; soft-max statistics in both directions where this one has a softplus and a sigmoid per element)
   backward   crossclr_sigmoid_backward   against   crossclr_infonce_backward (the same skeleton and 8 B^2 D flops), alone and with their
-             finish kernels
+             finish calls (one kernel, pairloss_backward_finish_kernel, with the divisor B or 2 B)
   module     SigmoidLoss forward + backward (unit rows in, normalize=True, s = 10, beta = -10)   against   eager PyTorch doing the same
              loss (F.normalize, mm, F.logsigmoid): fp32 against fp32 eager, bf16 against eager under torch.autocast(bfloat16)
   memory     torch.cuda.max_memory_allocated above the inputs for one fused step and for one eager step
