@@ -219,7 +219,8 @@ _SIGNATURES = {
     "crossclr_second_order": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _P, ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                              ctypes.POINTER(SampleWeights), ctypes.c_int, _P, _P, ctypes.c_long, ctypes.c_long, _P, _P, ctypes.c_size_t,
                                              _P, _P, ctypes.c_long, ctypes.c_long, _P, _P]),
-    # ABI version 7 (reporting aid): the kernel template the process's most recent forward (0) / gradient-product (1) launch went to
+    # reporting aid (ABI version 7: which = 0 forward, 1 gradient product; which = 2, the most recent row kernel, came later without an ABI
+    # change): the kernel template the process's most recent launch of that kind went to
     "crossclr_last_kernel": (ctypes.c_char_p, [ctypes.c_int]),
     # measurement aid (bench.py: the matrix pipe's sustained rate on this device, in the run that quotes it)
     "crossclr_mfma_sustained": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int, _P]),

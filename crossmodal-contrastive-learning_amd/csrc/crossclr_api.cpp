@@ -38,16 +38,20 @@ static int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-// which kernel template the most recent forward (0) / gradient-product (1) launch of this process went to (crossclr_last_kernel; pointers to
-// string literals, written whole: a reader on another thread -- autograd runs backward() on its own -- sees the old or the new name)
-static const char* volatile g_last_kernel[2] = {"", ""};
+// which kernel template the most recent forward (0) / gradient-product (1) / row-kernel (2: normalisation and lay-out, gradient finish) launch
+// of this process went to (crossclr_last_kernel; pointers to string literals, written whole: a reader on another thread -- autograd runs
+// backward() on its own -- sees the old or the new name)
+static const char* volatile g_last_kernel[3] = {"", "", ""};
 namespace crossclr {
-void note_kernel(int which, const char* name) { g_last_kernel[which & 1] = name; }
+void note_kernel(int which, const char* name) { g_last_kernel[which == 2 ? 2 : (which & 1)] = name; }
 }  // namespace crossclr
 static void note_generic_launch(const char* what) {      // (the generic kernels are launched from this file: their launch_status label names them)
     if (!strncmp(what, "fwd_sums_kernel", 15)) crossclr::note_kernel(0, what);
     else if (!strncmp(what, "bwd_kernel", 10) || !strncmp(what, "bwd_saved32_kernel", 18) || !strncmp(what, "bwd_saved_x3_kernel", 19))
         crossclr::note_kernel(1, what);
+    else if (!strncmp(what, "normalize_", 10) || !strcmp(what, "topk_pack_kernel") || !strncmp(what, "bwd_finish_", 11) ||
+             !strcmp(what, "pairloss_backward_finish_kernel") || !strcmp(what, "hardneg_backward_kernel"))
+        crossclr::note_kernel(2, what);
 }
 
 #ifdef CROSSCLR_EMU
@@ -66,7 +70,7 @@ static int launch_status(const char* what) {
 
 extern "C" int crossclr_abi_version(void) { return CROSSCLR_ABI_VERSION; }
 extern "C" const char* crossclr_last_error(void) { return g_err; }
-extern "C" const char* crossclr_last_kernel(int which) { return g_last_kernel[which & 1]; }
+extern "C" const char* crossclr_last_kernel(int which) { return g_last_kernel[which == 2 ? 2 : (which & 1)]; }
 extern "C" const char* crossclr_backend(void) {
 #ifdef CROSSCLR_EMU
     return "emu-host";
@@ -1308,7 +1312,7 @@ extern "C" int crossclr_backward_ranks(const crossclr_plan* plan, const void* xh
 
 template <typename TIN>
 static int backward_finish_t(const crossclr_plan* p, const float* gbuf, const void* v, const void* t, long ldv, long ldt,
-                             const float* inv_norm, float temperature, const double* grad_out, void* gv, void* gt,
+                             const float* inv_norm, double inv_tau, const double* grad_out, void* gv, void* gt,
                              long ldgv, long ldgt, const float* lw, void* stream, int prenormalized = 0) {
     Geo g; memset(&g, 0, sizeof(g));
     g.b = p->b; g.bpad = p->bpad; g.D = p->D; g.Dpad = p->Dpad;
@@ -1316,7 +1320,7 @@ static int backward_finish_t(const crossclr_plan* p, const float* gbuf, const vo
     if (p->D <= 256 * kRowCache) {      // row pairs: each raw row read once
 #define CROSSCLR_FINISH_PAIR(KC)                                                                                                        \
     LAUNCH((bwd_finish_pair_kernel<TIN, KC>), dim3((p->b + 3) / 4), block, stream, gbuf, p->bwd_slices, (const TIN*)v, (const TIN*)t, ldv, ldt, \
-           g, inv_norm, 1.0f / temperature, p->b * p->world, grad_out, (TIN*)gv, (TIN*)gt, ldgv, ldgt, lw, prenormalized)
+           g, inv_norm, inv_tau, p->b * p->world, grad_out, (TIN*)gv, (TIN*)gt, ldgv, ldgt, lw, prenormalized)
         switch ((p->D + 255) / 256) {      // (one instantiation per number of 256-element stretches a lane caches)
             case 1: CROSSCLR_FINISH_PAIR(1); break;
             case 2: CROSSCLR_FINISH_PAIR(2); break;
@@ -1327,7 +1331,7 @@ static int backward_finish_t(const crossclr_plan* p, const float* gbuf, const vo
         return launch_status("bwd_finish_pair_kernel");
     }
     LAUNCH((bwd_finish_kernel<TIN>), grid, block, stream, gbuf, p->bwd_slices, (const TIN*)v, (const TIN*)t, ldv, ldt, g, inv_norm,
-           1.0f / temperature, p->b * p->world, grad_out, (TIN*)gv, (TIN*)gt, ldgv, ldgt, lw, prenormalized);
+           inv_tau, p->b * p->world, grad_out, (TIN*)gv, (TIN*)gt, ldgv, ldgt, lw, prenormalized);
     return launch_status("bwd_finish_kernel");
 }
 
@@ -1349,19 +1353,29 @@ extern "C" int crossclr_backward_finish_w(const crossclr_plan* plan, const float
                                       grad_video, grad_text, ld_gvideo, ld_gtext, 0, stream);
 }
 
+// inv_tau: 1 / temperature as the kernels take it -- the float reciprocal of the float temperature for the loss (the value they have always
+// been handed), 2 / B in full precision for the ranking loss, whose divisor B * B is no temperature and must not carry a float rounding
+static int backward_finish_any(const crossclr_plan* plan, const float* gbuf, const void* video, const void* text, long ld_video, long ld_text,
+                               int in_dtype, const float* inv_norm, double inv_tau, const float* lw, const double* grad_out, void* grad_video,
+                               void* grad_text, long ld_gvideo, long ld_gtext, int prenormalized, void* stream) {
+    if (!plan || !gbuf || !video || !text || !inv_norm || !grad_out || !grad_video || !grad_text)
+        return fail(CROSSCLR_E_ARG, "NULL argument");
+    return with_in_dtype(in_dtype, [&](auto tin) {
+        return backward_finish_t<typename decltype(tin)::type>(plan, gbuf, video, text, ld_video, ld_text, inv_norm, inv_tau, grad_out, grad_video,
+                                                               grad_text, ld_gvideo, ld_gtext, lw, stream, prenormalized);
+    });
+}
+
 extern "C" int crossclr_backward_finish_p(const crossclr_plan* plan, const float* gbuf, const void* video,
                                           const void* text, long ld_video, long ld_text, int in_dtype,
                                           const float* inv_norm, float temperature, const crossclr_sample_weights* sw,
                                           const double* grad_out, void* grad_video, void* grad_text, long ld_gvideo,
                                           long ld_gtext, int prenormalized, void* stream) {
-    const float* lw = sw ? sw->loss_weight : nullptr;
     if (!plan || !gbuf || !video || !text || !inv_norm || !grad_out || !grad_video || !grad_text)
         return fail(CROSSCLR_E_ARG, "NULL argument");
     if (!(temperature > 0.f)) return fail(CROSSCLR_E_ARG, "temperature must be > 0");
-    return with_in_dtype(in_dtype, [&](auto tin) {
-        return backward_finish_t<typename decltype(tin)::type>(plan, gbuf, video, text, ld_video, ld_text, inv_norm, temperature, grad_out, grad_video,
-                                                               grad_text, ld_gvideo, ld_gtext, lw, stream, prenormalized);
-    });
+    return backward_finish_any(plan, gbuf, video, text, ld_video, ld_text, in_dtype, inv_norm, (double)(1.0f / temperature),
+                               sw ? sw->loss_weight : nullptr, grad_out, grad_video, grad_text, ld_gvideo, ld_gtext, prenormalized, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1465,9 +1479,9 @@ extern "C" int crossclr_maxmargin_backward_finish(const crossclr_plan* plan, con
     if (!plan || !ones || !active) return fail(CROSSCLR_E_ARG, "NULL argument");
     // bwd_finish_kernel with unit rows as given: out = (sum_slices * inv_tau / (2B) - partner * inv_tau / B * (lw_im + lw_s) / 2) * grad_out;
     // inv_tau = 2 / B and lw = the active-hinge counts make that (sum_slices - (a_im + a_s) partner) / B^2   (loss.py:33-41)
-    crossclr_sample_weights sw = {nullptr, nullptr, active};
-    return crossclr_backward_finish_p(plan, gbuf, im, s, ld_im, ld_s, in_dtype, ones, 0.5f * (float)plan->b, &sw, grad_out, grad_im, grad_s,
-                                      ld_gim, ld_gs, 1, stream);
+    // (2 / B as a double: the float reciprocal of a float "temperature" B / 2 left the fp64 gradients with a relative error of 2^-24)
+    return backward_finish_any(plan, gbuf, im, s, ld_im, ld_s, in_dtype, ones, 2.0 / (double)plan->b, active, grad_out, grad_im, grad_s, ld_gim,
+                               ld_gs, 1, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1159,7 +1159,7 @@ __global__ void __launch_bounds__(256) maxmargin_saved_kernel(const T* X, Geo g,
 // ---------------------------------------------------------------------------------------------
 template <typename TIN>
 __global__ void __launch_bounds__(256) bwd_finish_kernel(const float* gbuf, int nslices, const TIN* video, const TIN* text, long ldv,
-                                                         long ldt, Geo g, const float* inv_norm, float inv_tau,
+                                                         long ldt, Geo g, const float* inv_norm, double inv_tau,
                                                          int Bglobal, const double* grad_out, TIN* gvideo,
                                                          TIN* gtext, long ldgv, long ldgt, const float* lw, int prenormalized) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1284,7 +1284,7 @@ __global__ void __launch_bounds__(256) bwd_finish_kernel(const float* gbuf, int 
 // carries the registers of two stretches, not four (169 -> NN VGPRs: more rows in flight per CU for a kernel that only streams).
 template <typename TIN, int KC>
 __global__ void __launch_bounds__(256) bwd_finish_pair_kernel(const float* gbuf, int nslices, const TIN* video, const TIN* text, long ldv,
-                                                              long ldt, Geo g, const float* inv_norm, float inv_tau,
+                                                              long ldt, Geo g, const float* inv_norm, double inv_tau,
                                                               int Bglobal, const double* grad_out, TIN* gvideo,
                                                               TIN* gtext, long ldgv, long ldgt, const float* lw, int prenormalized) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;

@@ -276,8 +276,9 @@ __global__ void __launch_bounds__(256) hardneg_finish_kernel(const float* row_s,
 
 // ---------------------------------------------------------------------------------------------
 // Gradient of the hardest-negative loss: a deterministic gather, no atomics.  With O = the OTHER modality's rows (the caller's own tensors,
-// not the packed copy), idx / h = this modality's selections and hinges, idx' / h' = the other's:
-//   out[r] = ( [h[r] > 0] (O[idx[r]] - O[r])  -  [h'[r] > 0] O[r]  +  sum over i ascending, h'[i] > 0 and idx'[i] == r, of O[i] ) * grad_out / B^2
+// not the packed copy), idx / h = this modality's selections and hinges, idx' / h' = the other's, and an entry ACTIVE when its hinge is positive
+// and its index lies in [0, b) (index -1 = no candidate: such an entry contributes nothing, whatever its hinge):
+//   out[r] = ( [r active] (O[idx[r]] - O[r])  -  [r active'] O[r]  +  sum over i ascending, i active' and idx'[i] == r, of O[i] ) * grad_out / B^2
 //   grid = (ceil(b / 4), 2 modalities); one wave per output row, a lane owns columns lane + 64 k of a slab of 64 * kHardnegSlab columns
 //   (the scan is repeated per slab: once for D <= 1024).
 //   The scan: idx' and h' are staged through LDS kHardnegStage entries at a time; every thread marks which of the block's four rows its
@@ -320,7 +321,7 @@ __global__ void __launch_bounds__(256) hardneg_backward_kernel(const TIN* im, co
     if (live) {
         own = idx[r];
         own_active = h[r] > 0.f && own >= 0 && own < b;
-        other_active = h2[r] > 0.f;
+        other_active = h2[r] > 0.f && idx2[r] >= 0 && idx2[r] < b;      // (an entry without a candidate, index -1, contributes nothing)
     }
     for (int d0 = 0; d0 < D; d0 += 64 * kHardnegSlab) {
         ACC acc[kHardnegSlab];

@@ -521,7 +521,8 @@ int crossclr_topk_merge(const void* workspace, int nq, int ng, int k, int splits
  *   -inf likewise), hinge[2][bpad] (float; 0 likewise); pair_score[bpad] = S[i][i]; loss_sum (plan->loss_ws_doubles doubles):
  *   loss_sum[0] = sum of the 2 B hinges, loss_sum[1] = that / (B * B), from double partials added in a fixed order.
  * crossclr_hardneg_backward  the gradient of grad_out * loss w.r.t. the caller's own row-major tensors (not the packed copy), in their
- *   dtype: only active hinges (> 0) contribute -- hr[i]: s[jr[i]] - s[i] to grad_im[i], +im[i] to grad_s[jr[i]], -im[i] to grad_s[i];
+ *   dtype: only ACTIVE entries contribute (hinge > 0 and index in [0, B): an entry with index -1 adds nothing to any row, whatever its
+ *   hinge) -- hr[i]: s[jr[i]] - s[i] to grad_im[i], +im[i] to grad_s[jr[i]], -im[i] to grad_s[i];
  *   hc[j]: im[ic[j]] - im[j] to grad_s[j], +s[j] to grad_im[ic[j]], -s[j] to grad_im[j]; all scaled by grad_out[0] / (B * B) (a device
  *   double).  An O(B D) gather in a fixed order (fp32 accumulation, fp64 for fp64 inputs); every index is checked against [0, B) before
  *   it is used as an address.  grad_im or grad_s may be NULL (that gradient is not formed), not both.
@@ -748,7 +749,9 @@ int crossclr_second_order(const crossclr_plan* plan, const void* video, const vo
 
 /* Which kernels the most recent forward (which = 0) / gradient-product (which = 1) launch of this process went to: the kernel template's name
  * (e.g. "fast_fwd_pair_kernel", "fast_bwd_xfp_kernel"; "" before the first launch).  Reporting aid (bench.py labels its dominant kernel
- * with it); no reference counterpart.                                                                                   */
+ * with it); no reference counterpart.  which = 2: the most recent ROW kernel -- "normalize_kernel", "normalize_xf_kernel",
+ * "topk_pack_kernel", "bwd_finish_pair_kernel" (rows up to 1024 columns) or "bwd_finish_kernel", "pairloss_backward_finish_kernel",
+ * "hardneg_backward_kernel" -- for tests that pin which of them a shape selects.                                          */
 const char* crossclr_last_kernel(int which);
 
 /* Hardware assumption checks (MFMA fragment layouts, ds_read_b64_tr_b16 gather).  `out` is a
